@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: images/sec (512x512, 50 steps, SD-v1.4 + repellency) on N MI355X of one node.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, `config`).  `--full`
+adds everything else after the timed steps: live per-kernel roofline, stage split, the secondary legs (other precisions,
+latent-level workload, SD-v3, the 515-prompt job, live parity) and the CPU baseline.  `--dump-outputs DIR` writes what the
+last timed step returned (rank 0) as float32 .npy files, for output-for-output comparison of two builds.
 
 One "step" = one batch of P prompts taken END TO END through the README-default configuration of BASELINE config 2
 (configs/base/vanilla/safree_neg_prompt_config.json:26-28: safree = svf = lra = true; README.md:216-226), exactly as
@@ -592,6 +597,23 @@ def measure_sd3(dev, side, P, steps=50, refs_m=515):
     return res
 
 
+DUMP_SAMPLE = 1 << 22          # elements kept of an output larger than this: 16 MiB as float32
+
+
+def dump_outputs(out: torch.Tensor, directory: str, name: str) -> str:
+    """`--dump-outputs`: the array the last timed step returned to its caller, as float32 DIR/<name>.npy.  An output of more than
+    DUMP_SAMPLE elements (the e2e uint8 images: 50 MB at 64 prompts, 200 MB as float32) is written as a fixed sample instead:
+    DUMP_SAMPLE flat indices drawn with seed 0 and sorted, the same for every run of the same shape, in DIR/<name>_sample.npy."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    if out.numel() > DUMP_SAMPLE:
+        idx = torch.randint(out.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+        out, name = out.reshape(-1)[idx.to(out.device)], f"{name}_sample"
+    path = os.path.join(directory, f"{name}.npy")
+    np.save(path, out.float().cpu().numpy())
+    return path
+
+
 def _free_port() -> int:
     import socket
     with socket.socket() as s:
@@ -659,8 +681,12 @@ def main():
     ap.add_argument("--workload", default="e2e", choices=["e2e", "latent"],
                     help="e2e = the README-default call end to end (CLIP + SAFREE + 3-branch loop + VAE decode); latent = the round-1/2 "
                          "headline (prompt embeddings in, latents out, 2 CFG branches)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary legs (latent-level b = 2 figure, bf16x3 precision mode, live parity, SD-v3 config 4)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the roofline / stage figures, the secondary legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs (rank 0) to DIR/<name>.npy as float32 (at most 64 MB)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary legs (latent-level b = 2 figure, bf16x3 precision mode, live parity, SD-v3 config 4)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-latent-repeat", action="store_true", help="feed cat([latents] * 2) to a plain UNet plan")
     ap.add_argument("--no-tail-split", action="store_true",
                     help="a batch a few prompts over a multiple of 64 samples (e.g. --prompts-per-batch 65) as ONE forward per step (A/B of pipeline.tail_split)")
@@ -769,7 +795,43 @@ def main():
         assert out.dtype == torch.uint8 and tuple(out.shape) == (P, 512, 512, 3)
     else:
         assert torch.isfinite(out).all()
+    n_img = world * P * args.steps
+    value = n_img / dt
+    if e2e:
+        workload = (f"README-default end to end (safree = svf = lra = true, safree_neg_prompt_config.json:26-28): token ids -> CLIP -> "
+                    f"SAFREE projection -> {args.scheduler.upper()} {args.inference_steps} steps x UNet on 3 guidance branches with "
+                    f"per-prompt text switching + safe_denoiser.yaml repellency (kernel_fast, M={args.refs}, sigma 3.15, scale .33, "
+                    f"margin 1.6, window 780<=t<=1000) -> VAE decode -> uint8 512x512 images; SD-v1.4 UNet / CLIP / VAE with random "
+                    f"weights, {args.total_prompts}-prompt job sharded r::{world}, CFG 7.5, 120.5 TFLOP of UNet work per image")
+    else:
+        workload = (f"SD-v1.4 UNet (random weights) + safe_denoiser.yaml repellency (kernel_fast, M={args.refs}, sigma 3.15, scale "
+                    f".33, margin 1.6, window 780<=t<=1000), {args.total_prompts}-prompt job sharded r::{world}, CFG 7.5 (2 "
+                    f"branches), {args.scheduler.upper()} {args.inference_steps} steps, prompt embeddings in, 64x64x4 latents out")
+    line = {
+        "metric": "images/sec (512x512, 50 steps, SD-v1.4 + repellency)", "value": value, "unit": "images/sec",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": workload, "guidance_branches": nb, "text_encoder_precision": args.text_precision,
+                   "prompts_per_batch": P, "latent_repeat": unet.latent_repeat, "tail_split": tail_split_used, "images_timed": n_img, "beta_threshold": beta,
+                   "renoise_draws_rank0": renoise,
+                   "gate": {"r5_calibrated_beta_threshold": r5_beta, "margin": float(proc.beta_threshold_margin),
+                            "placement": placement,
+                            "fired_fraction_rank0": renoise / max(window_pairs, 1)},
+                   **({"safree": {"trigger_tokens_removed_rank0": safree_removed,
+                                  "mean_projected_text_steps_per_prompt": safree_steps / max(P * args.steps, 1)}} if e2e else {}),
+                   "parallelism": f"prompt-shard x{world}",
+                   "per_rank_images_per_sec": per_rank, "proj_ref_broadcast_ms": bcast_ms, "communicator_setup_ms": comm_ms,
+                   **({"rehearsal": "SDN_SHARE_GPU=1: ranks share the visible GPU(s) and talk over gloo -- a functional check of "
+                                    "the N > 1 path, NOT a scaling measurement"} if os.environ.get("SDN_SHARE_GPU") == "1" else {})},
+    }
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs, "images" if e2e else "latents")
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        return
 
+    # ---- --full: everything below is measured after the timed steps and adds to the line ----
     # ---- live kernel timing (HIP events on the launch stream) of one UNet forward at the benchmark shape ----
     x = torch.randn(nb * P // unet.latent_repeat, 4, 64, 64, device=dev)
     tb = unet.prepare_text(torch.randn(nb * P, 77, 768, device=dev))
@@ -892,35 +954,8 @@ def main():
     by_symbol = {name: sym_row(name) for name in top5}
     dom_row = by_symbol[dom]
     traffic, mfma_busy, mfma_extra = dom_row["traffic"], dom_row["mfma_busy"], dom_row.get("mfma_busy_detail")
-    n_img = world * P * args.steps
-    value = n_img / dt
     by_tf = {k_: v["flops"] / (v["ms"] * 1e-3) / 1e12 for k_, v in sorted(rows_acc.items(), key=lambda kv: -kv[1]["ms"])[:5]}
-    if e2e:
-        workload = (f"README-default end to end (safree = svf = lra = true, safree_neg_prompt_config.json:26-28): token ids -> CLIP -> "
-                    f"SAFREE projection -> {args.scheduler.upper()} {args.inference_steps} steps x UNet on 3 guidance branches with "
-                    f"per-prompt text switching + safe_denoiser.yaml repellency (kernel_fast, M={args.refs}, sigma 3.15, scale .33, "
-                    f"margin 1.6, window 780<=t<=1000) -> VAE decode -> uint8 512x512 images; SD-v1.4 UNet / CLIP / VAE with random "
-                    f"weights, {args.total_prompts}-prompt job sharded r::{world}, CFG 7.5, 120.5 TFLOP of UNet work per image")
-    else:
-        workload = (f"SD-v1.4 UNet (random weights) + safe_denoiser.yaml repellency (kernel_fast, M={args.refs}, sigma 3.15, scale "
-                    f".33, margin 1.6, window 780<=t<=1000), {args.total_prompts}-prompt job sharded r::{world}, CFG 7.5 (2 "
-                    f"branches), {args.scheduler.upper()} {args.inference_steps} steps, prompt embeddings in, 64x64x4 latents out")
-    line = {
-        "metric": "images/sec (512x512, 50 steps, SD-v1.4 + repellency)", "value": value, "unit": "images/sec",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": workload, "guidance_branches": nb, "text_encoder_precision": args.text_precision,
-                   "prompts_per_batch": P, "latent_repeat": unet.latent_repeat, "tail_split": tail_split_used, "images_timed": n_img, "beta_threshold": beta,
-                   "renoise_draws_rank0": renoise,
-                   "gate": {"r5_calibrated_beta_threshold": r5_beta, "margin": float(proc.beta_threshold_margin),
-                            "placement": placement,
-                            "fired_fraction_rank0": renoise / max(window_pairs, 1)},
-                   **({"safree": {"trigger_tokens_removed_rank0": safree_removed,
-                                  "mean_projected_text_steps_per_prompt": safree_steps / max(P * args.steps, 1)}} if e2e else {}),
-                   "parallelism": f"prompt-shard x{world}",
-                   "per_rank_images_per_sec": per_rank, "proj_ref_broadcast_ms": bcast_ms, "communicator_setup_ms": comm_ms,
-                   **({"rehearsal": "SDN_SHARE_GPU=1: ranks share the visible GPU(s) and talk over gloo -- a functional check of "
-                                    "the N > 1 path, NOT a scaling measurement"} if os.environ.get("SDN_SHARE_GPU") == "1" else {})},
+    line.update({
         "roofline": {"bound": "mfma", "achieved": achieved, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
                      "frac": achieved / PEAK_BF16_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
                      "mfma_busy": mfma_busy, "mfma_busy_source": mfma_src, **({"mfma_busy_detail": mfma_extra} if mfma_extra else {}),
@@ -950,7 +985,7 @@ def main():
                                 "single_query": {"us_per_call": rep1_ms * 1e3,
                                                  "achieved": rep1_bytes / (rep1_ms * 1e-3) / 1e9,
                                                  "frac": rep1_bytes / (rep1_ms * 1e-3) / 1e9 / PEAK_HBM_GBS}},
-    }
+    })
     if stages is not None:
         line["stages"] = stages
     if vae_block is not None:

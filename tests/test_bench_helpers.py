@@ -1,9 +1,12 @@
 """Host-side helpers of bench.py: plan label -> kernel symbol (the roofline block picks the dominant kernel by SYMBOL)
-and the choice of the newest sha-matched counter record."""
+and the choice of the newest sha-matched counter record; the --dump-outputs writer."""
 import json
 import os
 import re
 import sys
+
+import numpy as np
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -42,3 +45,18 @@ def test_counter_records_are_reported_only_for_the_running_library(tmp_path, mon
     rec, note = bench._pmc_records("traffic", "bbb")
     assert rec is None and "another build" in note and "round10" in note
     assert bench._pmc_records("mfma_util", "ccc")[0] is None
+
+
+def test_dump_outputs_writes_float32_whole_or_a_fixed_sample_under_64_mb(tmp_path):
+    lat = torch.randn(8, 4, 64, 64, generator=torch.Generator().manual_seed(1))
+    p = bench.dump_outputs(lat, str(tmp_path / "a"), "latents")                   # small: the whole array, shape kept
+    assert os.path.basename(p) == "latents.npy" and np.array_equal(np.load(p), lat.numpy())
+    img = torch.randint(0, 256, (64, 512, 512, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(2))
+    pa = bench.dump_outputs(img, str(tmp_path / "a"), "images")                    # the e2e default: 200 MB as float32
+    pb = bench.dump_outputs(img.clone(), str(tmp_path / "b"), "images")
+    a = np.load(pa)
+    assert os.path.basename(pa) == "images_sample.npy" and a.dtype == np.float32 and a.shape == (bench.DUMP_SAMPLE,)
+    assert os.path.getsize(pa) + os.path.getsize(p) <= 64 << 20
+    assert np.array_equal(a, np.load(pb))                                          # same positions on every run
+    idx = torch.randint(img.numel(), (bench.DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    assert np.array_equal(a, img.reshape(-1)[idx].float().numpy())
