@@ -347,6 +347,23 @@ int sdn_attention_x3(const void* q, const void* k, const void* v, void* out, int
                      int32_t nq, int32_t nk, int32_t head_dim, int32_t ldq, int32_t ldk, int32_t ldv,
                      int32_t ldo, float scale, void* stream);
 
+/* ---- SD-v3 MMDiT on fp32 storage (sdn_mmdit_config.dtype 2 = f32-input matrix cores, 3 = bf16x3 contractions) ----
+ * sdn_layernorm_mod_f32: the adaLN LayerNorm of sdn_layernorm_mod_bf16 (same arguments) on f32 rows x / out; statistics in f32;
+ *   c % 4 == 0, c <= 2048, x / scale / shift / out 16-byte aligned.
+ * sdn_patchify_f32: fp32 NCHW latent -> f32 patch rows [B*(H/p)*(W/p), C*p*p], column order (c, py, px) as sdn_patchify_bf16.
+ * sdn_joint_attention_f32: sdn_joint_attention's two-stream joint attention (same sdn_attn_segment2 descriptor) on f32 q / k / v /
+ *   out; mode 0 = exact f32 products (the kernel of sdn_attention_f32), 1 = bf16x3 products (that of sdn_attention_x3).  Rows of
+ *   either stream are addressed one by one (a query set or K / V tile may straddle n1; the concatenation is never materialised):
+ *   the result has the bits of sdn_attention_f32 / sdn_attention_x3 over the concatenated sequence.  head_dim 64 only; q / k / v
+ *   (both streams) 16-byte aligned, leading dimensions multiples of 4 floats. */
+int sdn_layernorm_mod_f32(const void* x, int64_t rows, int32_t c, float eps, const float* scale, const float* shift,
+                          int32_t ld_mod, int32_t rows_per_batch, void* out, void* stream);
+int sdn_patchify_f32(const float* latents, int32_t batch, int32_t c, int32_t h, int32_t w, int32_t p, void* out, void* stream);
+int sdn_joint_attention_f32(int32_t mode, const void* q, const void* k, const void* v, void* out,
+                            const sdn_attn_segment2* seg2_host, int32_t batch, int32_t heads, int32_t n_total,
+                            int32_t head_dim, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo, float scale,
+                            void* stream);
+
 /* ---- bf16x3 by operand expansion (round 4): the same three-term products as sdn_gemm_x3, on the LDS-DMA tiles of sdn_gemm_bf16.
  * A tensor x [rows, C] that a GEMM will read is kept as the bf16 TRIPLE [rows, 3C] = [hi(C) | lo(C) | hi(C)], hi = bf16(x),
  * lo = bf16(x - hi) (x = hi + lo to 2^-17); its weight W [N, K] as [N, 3K] with every K-group g (K itself, or the Cin of one
@@ -464,7 +481,9 @@ typedef struct sdn_mmdit_config {
   int32_t joint_dim, pooled_dim;         /* 4096, 2048                                                 */
   int32_t text_len;                      /* 333 = 77 CLIP + 256 T5 tokens                              */
   int32_t time_dim;                      /* 256 sinusoidal features                                    */
-  int32_t dtype;                         /* 0 = bf16, 1 = fp16 (the reference runs SD-v3 in fp16)      */
+  int32_t dtype;                         /* 0 = bf16, 1 = fp16 (the reference runs SD-v3 in fp16); 2 = fp32 storage on
+                                          * the f32-input matrix cores (sdn_gemm_f32), 3 = fp32 storage with bf16x3
+                                          * contractions (sdn_gemm_x3): f32 weights, text and pooled projections */
 } sdn_mmdit_config;
 int sdn_mmdit_create(const sdn_mmdit_config* cfg_host, sdn_unet** out_host);
 /* v = transformer(latents [B,16,S,S] fp32, t, text [B,text_len,joint_dim] 16-bit, pooled [B,pooled_dim] 16-bit)

@@ -151,6 +151,10 @@ SIGNATURES = {
     "sdn_patchify_bf16": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "sdn_patchify_f16": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "sdn_unpatchify_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "sdn_layernorm_mod_f32": (C.c_int, [_vp, _i64, _i32, _f32, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "sdn_patchify_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "sdn_joint_attention_f32": (C.c_int, [_i32, _vp, _vp, _vp, _vp, C.POINTER(AttnSegment2), _i32, _i32, _i32, _i32, _i32,
+                                          _i32, _i32, _i32, _f32, _vp]),
     "sdn_repeat": (C.c_int, [_vp, _sz, _i32, _vp, _vp]),
     "sdn_vae_decoder_create": (C.c_int, [C.POINTER(VaeConfig), C.POINTER(_vp)]),
     "sdn_vae_decode": (C.c_int, [_vp, _vp, _vp, _f32, _vp, _i32, _vp, _sz, _vp]),

@@ -408,11 +408,26 @@ k_layernorm_f32(const float* __restrict__ x, long rows, int c, float eps, const 
 // (k-step s, lane group g  <->  key 4g + s on both operands).  Exponentials are expf(x - max): the reference's softmax.
 // ================================================================================================
 // MASK (CLIP text encoder, sdn_masked_attention_f32): causal key <= query and an optional per-sample key-padding mask [B, nk].
-template <int HD, bool MASK = false>
+// SEG (MMDiT joint attention, sdn_joint_attention_f32): rows [0, n1) of the sequence live in q / k / v / out ([B, n1, ld]),
+// rows [n1, n) in the second stream's buffers ([B, n - n1, ld2]); every row is addressed on its own, so a query set or a
+// K / V tile may straddle n1 and the concatenation is never materialised.  SEG = false compiles to the single-stream kernel's
+// instructions (the flag only adds the trailing `sg` argument).
+struct Seg2F {
+  const float* q2; const float* k2; const float* v2; float* out2;
+  int n1, ldq2, ldk2, ldv2, ldo2;
+};
+// Row `row` of sample b in a (possibly two-stream) [B, n, ld] tensor.
+template <bool SEG, typename P>
+__device__ __forceinline__ P* seg_row(P* p1, P* p2, int ld1, int ld2, int n1, int n, int b, int row) {
+  if (SEG && row >= n1) return p2 + ((long)b * (n - n1) + (row - n1)) * ld2;
+  return p1 + ((long)b * (SEG ? n1 : n) + row) * ld1;
+}
+
+template <int HD, bool MASK = false, bool SEG = false>
 __global__ void __launch_bounds__(256)
 k_attention_f32(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, float* __restrict__ out,
                 int heads, int nq, int nk, int ldq, int ldk, int ldv, int ldo, float scale, int causal = 0,
-                const int* __restrict__ kmask = nullptr) {
+                const int* __restrict__ kmask = nullptr, const Seg2F sg = Seg2F{}) {
   constexpr int DB = (HD + 15) / 16, DP = DB * 16;                          // head dim padded to whole 16-column blocks
   constexpr int KS = HD / 4;                                               // k-steps of the score product (HD % 4 == 0)
   constexpr int LDK = ((HD + 29) / 32) * 32 + 2;                            // rows 2 banks apart mod 32: conflict-free reads
@@ -425,7 +440,8 @@ k_attention_f32(const float* __restrict__ q, const float* __restrict__ k, const 
   const int b = bh / heads, h = bh - b * heads;
   const int qi = qb * 64 + wid * 16 + fr;                                  // this lane's query
   const bool q_ok = qi < nq;
-  const float* qp = q + ((long)b * nq + (q_ok ? qi : 0)) * ldq + h * HD;
+  const float* qp = SEG ? seg_row<true>(q, sg.q2, ldq, sg.ldq2, sg.n1, nq, b, q_ok ? qi : 0) + h * HD
+                        : q + ((long)b * nq + (q_ok ? qi : 0)) * ldq + h * HD;
   float qf[KS];                                                            // B operand of k-step s: Q[query fr][dim 4s + fq]
 #pragma unroll
   for (int s = 0; s < KS; ++s) qf[s] = q_ok ? qp[4 * s + fq] * scale : 0.f;
@@ -442,8 +458,13 @@ k_attention_f32(const float* __restrict__ q, const float* __restrict__ k, const 
       const int r = i / (HD / 4), c4 = (i - r * (HD / 4)) * 4;
       f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
       if (k0 + r < nk) {
-        kv = *reinterpret_cast<const f32x4*>(kb + (long)(k0 + r) * ldk + c4);
-        vv = *reinterpret_cast<const f32x4*>(vb + (long)(k0 + r) * ldv + c4);
+        if (SEG) {
+          kv = *reinterpret_cast<const f32x4*>(seg_row<true>(k, sg.k2, ldk, sg.ldk2, sg.n1, nk, b, k0 + r) + h * HD + c4);
+          vv = *reinterpret_cast<const f32x4*>(seg_row<true>(v, sg.v2, ldv, sg.ldv2, sg.n1, nk, b, k0 + r) + h * HD + c4);
+        } else {
+          kv = *reinterpret_cast<const f32x4*>(kb + (long)(k0 + r) * ldk + c4);
+          vv = *reinterpret_cast<const f32x4*>(vb + (long)(k0 + r) * ldv + c4);
+        }
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) { sk[r * LDK + c4 + e] = kv[e]; sv[r * LDV + c4 + e] = vv[e]; }
@@ -488,7 +509,7 @@ k_attention_f32(const float* __restrict__ q, const float* __restrict__ k, const 
   // O^T accumulator: column = query fr, row = dim 16d + 4 fq + e
   if (!q_ok) return;
   const float inv = 1.0f / lrun;
-  float* op = out + ((long)b * nq + qi) * ldo + h * HD;
+  float* op = SEG ? seg_row<true>(out, sg.out2, ldo, sg.ldo2, sg.n1, nq, b, qi) + h * HD : out + ((long)b * nq + qi) * ldo + h * HD;
 #pragma unroll
   for (int d = 0; d < DB; ++d)
 #pragma unroll
@@ -497,6 +518,7 @@ k_attention_f32(const float* __restrict__ q, const float* __restrict__ k, const 
       if (dim < HD) op[dim] = o[d][e] * inv;
     }
 }
+
 
 // CLIPTextEmbeddings in f32: out[b, t, :] = token_embedding[ids[b, t]] + position_embedding[t]
 __global__ void __launch_bounds__(256)
@@ -781,10 +803,11 @@ k_gemm_x3(const GemmArgsF g) {
 //   O^T[dim][query] += V^T . P^T as ONE 32-key contraction per 16-dim block: k slot (lane group g, s) <-> key 4 g + s (s < 4)
 //     or 16 + 4 g + (s - 4): exactly the eight probabilities the lane already holds, so P goes from the score accumulators to
 //     the B operand in registers; V^T sits in LDS [dim][32 key slots] in that slot order (transposed and permuted by staging).
-template <int HD, int QS>
+// SEG: the two-stream addressing of k_attention_f32 (sdn_joint_attention_f32 mode 1; no triple output).
+template <int HD, int QS, bool SEG = false>
 __global__ void __launch_bounds__(256)
 k_attention_x3(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, float* __restrict__ out,
-               int heads, int nq, int nk, int ldq, int ldk, int ldv, int ldo, float scale, int triple) {
+               int heads, int nq, int nk, int ldq, int ldk, int ldv, int ldo, float scale, int triple, const Seg2F sg = Seg2F{}) {
   constexpr int NB = (HD + 31) / 32, HDP = NB * 32;                         // score product: head dim in blocks of 32
   constexpr int DB = (HD + 15) / 16, DP = DB * 16;                          // output dims in blocks of 16
   constexpr int LK = HDP + 8, LV = 40;                                      // LDS row lengths (bf16 elements)
@@ -805,7 +828,8 @@ k_attention_x3(const float* __restrict__ q, const float* __restrict__ k, const f
 #pragma unroll
   for (int s = 0; s < QS; ++s) {
     const int qi = qb * QB + 64 * s + wid * 16 + fr;
-    const float* qp = q + ((long)b * nq + (qi < nq ? qi : 0)) * ldq + h * HD;
+    const float* qp = SEG ? seg_row<true>(q, sg.q2, ldq, sg.ldq2, sg.n1, nq, b, qi < nq ? qi : 0) + h * HD
+                          : q + ((long)b * nq + (qi < nq ? qi : 0)) * ldq + h * HD;
 #pragma unroll
     for (int n = 0; n < NB; ++n) {
       const int d0 = 32 * n + 8 * fq;
@@ -830,8 +854,13 @@ k_attention_x3(const float* __restrict__ q, const float* __restrict__ k, const f
       if (i < NV4) {
         const int r = i / (HD / 4), c4 = (i - r * (HD / 4)) * 4;
         if (k0 + r < nk) {
-          rk[it] = *reinterpret_cast<const f32x4*>(kb + (long)(k0 + r) * ldk + c4);
-          rv[it] = *reinterpret_cast<const f32x4*>(vb + (long)(k0 + r) * ldv + c4);
+          if (SEG) {
+            rk[it] = *reinterpret_cast<const f32x4*>(seg_row<true>(k, sg.k2, ldk, sg.ldk2, sg.n1, nk, b, k0 + r) + h * HD + c4);
+            rv[it] = *reinterpret_cast<const f32x4*>(seg_row<true>(v, sg.v2, ldv, sg.ldv2, sg.n1, nk, b, k0 + r) + h * HD + c4);
+          } else {
+            rk[it] = *reinterpret_cast<const f32x4*>(kb + (long)(k0 + r) * ldk + c4);
+            rv[it] = *reinterpret_cast<const f32x4*>(vb + (long)(k0 + r) * ldv + c4);
+          }
         }
       }
     }
@@ -921,7 +950,7 @@ k_attention_x3(const float* __restrict__ q, const float* __restrict__ k, const f
     const int qi = qb * QB + 64 * s + wid * 16 + fr;
     if (qi >= nq) continue;
     const float inv = 1.0f / lrun[s];
-    if (triple) {                                                           // [hi(ldo) | lo(ldo) | hi(ldo)] rows: the to_out GEMM's A operand
+    if (!SEG && triple) {                                                           // [hi(ldo) | lo(ldo) | hi(ldo)] rows: the to_out GEMM's A operand
       unsigned short* row3 = reinterpret_cast<unsigned short*>(out) + ((long)b * nq + qi) * 3 * ldo;
 #pragma unroll
       for (int d = 0; d < DB; ++d) {
@@ -933,7 +962,7 @@ k_attention_x3(const float* __restrict__ q, const float* __restrict__ k, const f
       }
       continue;
     }
-    float* op = out + ((long)b * nq + qi) * ldo + h * HD;
+    float* op = SEG ? seg_row<true>(out, sg.out2, ldo, sg.ldo2, sg.n1, nq, b, qi) + h * HD : out + ((long)b * nq + qi) * ldo + h * HD;
 #pragma unroll
     for (int d = 0; d < DB; ++d)
 #pragma unroll
@@ -943,6 +972,7 @@ k_attention_x3(const float* __restrict__ q, const float* __restrict__ k, const f
       }
   }
 }
+
 
 // f32 [rows, c1] (++ f32 [rows, c2]) -> triple [rows, 3 (c1 + c2)]: raw residual-stream tensors a GEMM reads (shortcut convs over
 // the skip concatenation, down / up-sampling convs, proj_out), text states.  One pass: 4 B read, 6 B written per element.
@@ -976,6 +1006,66 @@ k_expand3_weights(const float* __restrict__ w, long rows, int cols, int group, u
     const unsigned short hi = bf16_rne(v), lo = bf16_rne(v - __uint_as_float((unsigned)hi << 16));
     unsigned short* o = out + r * 3 * cols + (long)gi * 3 * group + ci;
     o[0] = hi; o[group] = hi; o[2 * group] = lo;
+  }
+}
+
+// ================================================================================================
+// MMDiT front end and adaLN in f32 (sdn_mmdit_config.dtype 2 / 3).
+// adaLN LayerNorm: out = LN(x) * (1 + scale[b]) + shift[b], scale / shift per-sample f32 rows of leading dimension ld_mod (sample of
+// a row = row / rows_per_batch).  One wave per row, the row in registers (NV float4 per lane: C <= 256 NV); mean, then the centred
+// sum of squares, both f32 over the registers (the reference's fp32 layer_norm); one 16-byte store per lane and quad.
+template <int NV>
+__global__ void __launch_bounds__(256)
+k_layernorm_mod_f32(const float* __restrict__ x, long rows, int c, float eps, const float* __restrict__ scale,
+                    const float* __restrict__ shift, int ld_mod, int rows_per_batch, float* __restrict__ out) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int lane = threadIdx.x & 63, c4 = c >> 2;
+  const float* xr = x + row * c;
+  f32x4 v[NV];
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int q = lane + 64 * j;
+    v[j] = q < c4 ? *reinterpret_cast<const f32x4*>(xr + 4 * q) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    s += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
+  }
+  const float mean = wave_sum(s) / (float)c;
+  float qs = 0.f;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    if (lane + 64 * j < c4) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { const float d = v[j][e] - mean; qs = fmaf(d, d, qs); }
+    }
+  }
+  const float rstd = 1.0f / sqrtf(wave_sum(qs) / (float)c + eps);
+  const long b = row / rows_per_batch;
+  const float* sc = scale + b * ld_mod;
+  const float* sh = shift + b * ld_mod;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int q = lane + 64 * j;
+    if (q >= c4) continue;
+    const f32x4 ga = *reinterpret_cast<const f32x4*>(sc + 4 * q), be = *reinterpret_cast<const f32x4*>(sh + 4 * q);
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = (v[j][e] - mean) * rstd * (1.f + ga[e]) + be[e];
+    *reinterpret_cast<f32x4*>(out + row * c + 4 * q) = o;
+  }
+}
+
+// patchify: fp32 NCHW latent [B,C,H,W] -> f32 [B*(H/p)*(W/p), C*p*p], column order (c, py, px) as k_patchify (sdn_norm.hip)
+__global__ void __launch_bounds__(256)
+k_patchify_f32(const float* __restrict__ lat, int B, int C, int H, int W, int p, float* __restrict__ out) {
+  const int hp = H / p, wp = W / p, K = C * p * p;
+  const long total = (long)B * hp * wp * K;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const int k = (int)(e % K);
+    const long tok = e / K;
+    const int px = k % p, py = (k / p) % p, ch = k / (p * p);
+    const int tx = (int)(tok % wp), ty = (int)((tok / wp) % hp), b = (int)(tok / ((long)wp * hp));
+    out[e] = lat[(((long)b * C + ch) * H + ty * p + py) * W + tx * p + px];
   }
 }
 
@@ -1171,6 +1261,12 @@ extern "C" int sdn_layernorm_f32_triple(const void* x, int64_t rows, int32_t c, 
   return layernorm_f32_impl(1, x, rows, c, eps, gamma, beta, out_triple, stream);
 }
 
+// query sets per wave of the split attention kernels: as many as the registers hold, but not more than the query count fills
+static int x3_qs_cap() {
+  static const int v = getenv("SDN_X3_QS") ? atoi(getenv("SDN_X3_QS")) : 2;      /* tuning knob (tools/bench_precision.py) */
+  return v;
+}
+
 static int attention_f32_storage(int x3, int triple, const void* q, const void* k, const void* v, void* out, int32_t batch, int32_t heads,
                                  int32_t nq, int32_t nk, int32_t head_dim, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo,
                                  float scale, void* stream) {
@@ -1183,7 +1279,7 @@ static int attention_f32_storage(int x3, int triple, const void* q, const void* 
   if (grid > 0x7fffffffL) return SDN_E_INVALID;
   const float* qf = (const float*)q; const float* kf = (const float*)k; const float* vf = (const float*)v;
   // query sets per wave of the split kernel: as many as the registers hold, but not more than the query count fills
-  static const int qs_cap = getenv("SDN_X3_QS") ? atoi(getenv("SDN_X3_QS")) : 2;      /* tuning knob (tools/bench_precision.py) */
+  const int qs_cap = x3_qs_cap();
 #define SDN_ATTN_F32(HD, QSMAX)                                                                                       \
   if (x3) {                                                                                                           \
     const int QS_ = QSMAX < qs_cap ? QSMAX : qs_cap;                                                                                        \
@@ -1307,5 +1403,74 @@ extern "C" int sdn_clip_embed_f32(const int32_t* input_ids, const void* token_em
   if (g > 4096) g = 4096;
   hipLaunchKernelGGL(k_clip_embed_f32, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, input_ids, (const float*)token_embedding,
                      (const float*)position_embedding, (long)rows, seq_len, hidden, vocab, (float*)out);
+  return sdn_launch_status();
+}
+
+// ---- MMDiT in the fp32-storage modes (sdn_mmdit_config.dtype 2 / 3) --------------------------------------------------------------
+extern "C" int sdn_layernorm_mod_f32(const void* x, int64_t rows, int32_t c, float eps, const float* scale, const float* shift,
+                                     int32_t ld_mod, int32_t rows_per_batch, void* out, void* stream) {
+  if (!x || !scale || !shift || !out || rows < 0 || c <= 0 || (c & 3) || c > 2048 || rows_per_batch <= 0 || ld_mod < c ||
+      (ld_mod & 3) || !al16(x) || !al16(scale) || !al16(shift) || !al16(out))
+    return SDN_E_INVALID;
+  if (rows == 0) return SDN_OK;
+  const long blocks = (rows + 3) / 4;
+  if (blocks > 0x7fffffffL) return SDN_E_INVALID;
+#define SDN_LNM_F32(NV)                                                                                                         \
+  hipLaunchKernelGGL((k_layernorm_mod_f32<NV>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)x, (long)rows, \
+                     c, eps, scale, shift, ld_mod, rows_per_batch, (float*)out)
+  if (c <= 512) SDN_LNM_F32(2);
+  else if (c <= 1024) SDN_LNM_F32(4);
+  else SDN_LNM_F32(8);
+#undef SDN_LNM_F32
+  return sdn_launch_status();
+}
+
+extern "C" int sdn_patchify_f32(const float* latents, int32_t batch, int32_t c, int32_t h, int32_t w, int32_t p, void* out, void* stream) {
+  if (!latents || !out || batch < 0 || c <= 0 || h <= 0 || w <= 0 || p <= 0 || h % p || w % p) return SDN_E_INVALID;
+  if (batch == 0) return SDN_OK;
+  const long total = (long)batch * c * h * w;
+  long grid = (total + 255) / 256;
+  if (grid > 2048) grid = 2048;
+  hipLaunchKernelGGL(k_patchify_f32, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, latents, batch, c, h, w, p, (float*)out);
+  return sdn_launch_status();
+}
+
+// Joint attention over two token streams on f32 storage: the kernels of sdn_attention_f32 (mode 0) / sdn_attention_x3 (mode 1)
+// with per-row two-stream addressing, launched with the grid and query-set count the single-stream entry points pick for
+// nq = nk = n_total -- the same products in the same order as those kernels over the concatenated sequence.
+extern "C" int sdn_joint_attention_f32(int32_t mode, const void* q, const void* k, const void* v, void* out, const sdn_attn_segment2* s2,
+                                       int32_t batch, int32_t heads, int32_t n_total, int32_t head_dim, int32_t ldq, int32_t ldk,
+                                       int32_t ldv, int32_t ldo, float scale, void* stream) {
+  if ((mode != 0 && mode != 1) || !s2 || !q || !k || !v || !out || head_dim != 64 || batch < 0 || heads <= 0 || n_total <= 0)
+    return SDN_E_INVALID;
+  if (!s2->q2 || !s2->k2 || !s2->v2 || !s2->out2 || s2->n1 <= 0 || s2->n1 >= n_total) return SDN_E_INVALID;
+  const int w = heads * 64;
+  if (ldq < w || ldk < w || ldv < w || ldo < w || s2->ldq2 < w || s2->ldk2 < w || s2->ldv2 < w || s2->ldo2 < w) return SDN_E_INVALID;
+  if ((ldq | ldk | ldv | s2->ldq2 | s2->ldk2 | s2->ldv2) & 3) return SDN_E_INVALID;
+  if (!al16(q) || !al16(k) || !al16(v) || !al16(s2->q2) || !al16(s2->k2) || !al16(s2->v2) ||
+      ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(s2->out2)) & 3))
+    return SDN_E_INVALID;
+  if (batch == 0) return SDN_OK;
+  const long grid = (long)batch * heads * ((n_total + 63) / 64);
+  if (grid > 0x7fffffffL) return SDN_E_INVALID;
+  const Seg2F sg{(const float*)s2->q2, (const float*)s2->k2, (const float*)s2->v2, (float*)s2->out2, s2->n1, s2->ldq2, s2->ldk2,
+                 s2->ldv2, s2->ldo2};
+  const float* qf = (const float*)q; const float* kf = (const float*)k; const float* vf = (const float*)v;
+  hipStream_t st = (hipStream_t)stream;
+  if (mode == 0) {
+    hipLaunchKernelGGL((k_attention_f32<64, false, true>), dim3((unsigned)grid), dim3(256), 0, st, qf, kf, vf, (float*)out, heads, n_total, n_total, ldq, ldk,
+                       ldv, ldo, scale, 0, nullptr, sg);
+    return sdn_launch_status();
+  }
+  const int qs = x3_qs_cap() < 4 ? x3_qs_cap() : 4;                           // as attention_f32_storage for head_dim 64
+  if (qs >= 4 && n_total >= 256)
+    hipLaunchKernelGGL((k_attention_x3<64, 4, true>), dim3((unsigned)((long)batch * heads * ((n_total + 255) / 256))), dim3(256), 0, st, qf, kf, vf,
+                       (float*)out, heads, n_total, n_total, ldq, ldk, ldv, ldo, scale, 0, sg);
+  else if (qs >= 2 && n_total >= 128)
+    hipLaunchKernelGGL((k_attention_x3<64, 2, true>), dim3((unsigned)((long)batch * heads * ((n_total + 127) / 128))), dim3(256), 0, st, qf, kf, vf,
+                       (float*)out, heads, n_total, n_total, ldq, ldk, ldv, ldo, scale, 0, sg);
+  else
+    hipLaunchKernelGGL((k_attention_x3<64, 1, true>), dim3((unsigned)grid), dim3(256), 0, st, qf, kf, vf, (float*)out, heads, n_total, n_total, ldq, ldk,
+                       ldv, ldo, scale, 0, sg);
   return sdn_launch_status();
 }

@@ -706,15 +706,18 @@ struct Builder {
     o.gd.residual_bcast = residual_bcast;
     o.a = a; o.w = w; o.bias = bias; o.rowbias = rowbias; o.rowgate = rowgate; o.residual = residual; o.out = out;
     o.flops = 2.0 * (double)M * N * K;
-    o.bytes = 2.0 * ((double)M * K + (double)N * K + (double)M * N);
-    snprintf(o.label, sizeof(o.label), "k_gemm<%d>", sdn_gemm_pick_tile((int)M, N, K, act_, residual.space != SP_NONE || rowgate.space != SP_NONE));
+    o.bytes = es * ((double)M * K + (double)N * K + (double)M * N);
+    if (es == 4)                      // MMDiT fp32-storage plans: sdn_gemm_f32, or sdn_gemm_x3 (its f32 tile below 64 rows)
+      snprintf(o.label, sizeof(o.label), (u->mcfg.dtype == 3 && M >= 64) ? "k_gemm_x3" : "k_gemm_f32");
+    else
+      snprintf(o.label, sizeof(o.label), "k_gemm<%d>", sdn_gemm_pick_tile((int)M, N, K, act_, residual.space != SP_NONE || rowgate.space != SP_NONE));
     push_gemm(o);
   }
   void ln_mod(const Act& x, int64_t rows, int rows_per_batch, Ref scale, Ref shift, int ld, const Act& out) {
     Op o; o.kind = OP_LN; o.a = R(x); o.rows = rows; o.c1 = x.C; o.eps = 1e-6f; o.w = scale; o.bias = shift; o.out = R(out);
     o.mod = 1; o.ld_mod = ld; o.hw = rows_per_batch;
-    o.bytes = 2.0 * 2.0 * (double)rows * x.C;
-    snprintf(o.label, sizeof(o.label), "k_layernorm");
+    o.bytes = 2.0 * es * (double)rows * x.C;
+    snprintf(o.label, sizeof(o.label), es == 4 ? "k_layernorm_mod_f32" : "k_layernorm");
     plan->ops.push_back(o);
   }
   Ref fcol(int col) const { return Ref{SP_WS, tproj.off + (int64_t)col * 4}; }   // column of the stacked adaLN output
@@ -753,7 +756,7 @@ struct Builder {
       for (size_t j = 0; j < mods.size(); ++j) {
         Ref r = param(mods[j].first + ".weight", SDN_P_MAT, mods[j].second, C);
         if (j == 0) adw = r; else if (r.off != expect) { fprintf(stderr, "libsdn: adaLN weights not contiguous\n"); abort(); }
-        expect = r.off + (int64_t)mods[j].second * C * 2;
+        expect = r.off + (int64_t)mods[j].second * C * es;
       }
       expect = -1;
       for (size_t j = 0; j < mods.size(); ++j) {
@@ -767,7 +770,8 @@ struct Builder {
     // ---- conditioning: silu(time_emb + pooled_emb) -> all modulation vectors ----
     plan->tscalar_off = arena.alloc(256);
     Act tsin = act(B, c.time_dim);
-    { Op o; o.kind = OP_TEMB; o.batch = B; o.c1 = c.time_dim; o.out = R(tsin); snprintf(o.label, sizeof(o.label), "k_temb"); plan->ops.push_back(o); }
+    { Op o; o.kind = OP_TEMB; o.batch = B; o.c1 = c.time_dim; o.out = R(tsin); snprintf(o.label, sizeof(o.label), es == 4 ? "k_temb_f32" : "k_temb");
+      plan->ops.push_back(o); }
     Act th = act(B, C);
     gemm_ex(B, C, c.time_dim, R(tsin), t1w, t1b, R(th), SDN_ACT_SILU, Ref(), SDN_OUT_BF16, Ref(), Ref(), 0, 0);
     drop(tsin);
@@ -787,7 +791,7 @@ struct Builder {
     // ---- token streams ----
     Act patches = act((int64_t)B * N, KP);
     { Op o; o.kind = OP_PATCHIFY; o.batch = B; o.c1 = c.in_channels; o.hw = S; o.patch = ps; o.a = Ref{SP_LATENTS, 0}; o.out = R(patches);
-      o.bytes = (double)B * N * KP * 6.0; snprintf(o.label, sizeof(o.label), "k_patchify"); plan->ops.push_back(o); }
+      o.bytes = (double)B * N * KP * (4.0 + es); snprintf(o.label, sizeof(o.label), es == 4 ? "k_patchify_f32" : "k_patchify"); plan->ops.push_back(o); }
     Act x = act((int64_t)B * N, C, N);
     gemm_ex((int64_t)B * N, C, KP, R(patches), pew, peb, R(x), SDN_ACT_NONE, pos, SDN_OUT_BF16, Ref(), Ref(), N, 0, 1);
     drop(patches);
@@ -819,12 +823,13 @@ struct Builder {
       Act ax = act((int64_t)B * N, C, N), ac = act((int64_t)B * T, C, T);
       {
         Op o; o.kind = OP_ATTN; o.batch = B; o.heads = c.num_heads; o.nq = N + T; o.nk = N + T; o.hd = c.head_dim;
-        o.a = R(qx); o.k = Ref{SP_WS, qx.off + (int64_t)C * 2}; o.v = Ref{SP_WS, qx.off + (int64_t)2 * C * 2}; o.out = R(ax);
-        o.q2 = R(qc); o.k2 = Ref{SP_WS, qc.off + (int64_t)C * 2}; o.v2 = Ref{SP_WS, qc.off + (int64_t)2 * C * 2}; o.out2 = R(ac);
+        o.a = R(qx); o.k = Ref{SP_WS, qx.off + (int64_t)C * es}; o.v = Ref{SP_WS, qx.off + (int64_t)2 * C * es}; o.out = R(ax);
+        o.q2 = R(qc); o.k2 = Ref{SP_WS, qc.off + (int64_t)C * es}; o.v2 = Ref{SP_WS, qc.off + (int64_t)2 * C * es}; o.out2 = R(ac);
         o.n1 = N; o.ldq = o.ldk = o.ldv = 3 * C; o.ldo = C; o.scale = 1.0f / sqrtf((float)c.head_dim);
         o.flops = 4.0 * (double)B * o.heads * (double)(N + T) * (double)(N + T) * o.hd;
-        o.bytes = 2.0 * (double)B * (N + T) * C * 4.0;
-        snprintf(o.label, sizeof(o.label), "k_attn<%d>", o.hd);
+        o.bytes = es * (double)B * (N + T) * C * 4.0;
+        if (es == 4) snprintf(o.label, sizeof(o.label), u->mcfg.dtype == 3 ? "k_attention_x3/seg" : "k_attention_f32/seg");
+        else snprintf(o.label, sizeof(o.label), "k_attn<%d>", o.hd);
         plan->ops.push_back(o);
         plan->flops += o.flops; plan->attn_flops += o.flops;
       }
@@ -1331,7 +1336,7 @@ Plan* get_plan(sdn_unet* u, int batch) {
   p.batch = batch;
   Builder b{u, &p};
   b.B = batch;
-  b.es = (!u->is_vae && !u->is_mmdit && u->cfg.dtype >= 2) ? 4 : 2;       // fp32 storage: SD-v1.4 UNet and CLIP text encoder plans
+  b.es = (!u->is_vae && (u->is_mmdit ? u->mcfg.dtype : u->cfg.dtype) >= 2) ? 4 : 2;   // fp32 storage: SD-v1.4 UNet, CLIP and MMDiT plans
   b.x3t = !u->is_vae && !u->is_mmdit && !u->is_clip && u->cfg.dtype == 3 && u->x3_expand;
   if (u->is_clip) b.build_clip(); else if (u->is_vae_encoder) b.build_vae_encoder(); else if (u->is_vae) b.build_vae(); else if (u->is_mmdit) b.build_mmdit(); else b.build();
   return &p;
@@ -1390,7 +1395,7 @@ int sdn_mmdit_create(const sdn_mmdit_config* cfg, sdn_unet** out) {
       C % 128 != 0 || cfg->joint_dim % 64 != 0 || cfg->pooled_dim % 64 != 0 || cfg->time_dim % 64 != 0 ||
       (cfg->in_channels * cfg->patch_size * cfg->patch_size) % 64 != 0 ||
       (cfg->out_channels * cfg->patch_size * cfg->patch_size) % 32 != 0 || cfg->text_len <= 0 || cfg->dtype < 0 ||
-      cfg->dtype > 1 || C > 2048)
+      cfg->dtype > 3 || C > 2048)
     return SDN_E_INVALID;
   sdn_unet* u = new sdn_unet();
   memset(&u->cfg, 0, sizeof(u->cfg));
@@ -1642,8 +1647,9 @@ static int launch_ops(sdn_unet* u, Plan* p, const char* W, const char* WS, const
   auto P = [&](const Ref& r) { return resolve(r, W, WS, L, T, O, PL, KV); };
   size_t opi = 0;
   const bool f16 = (u->is_mmdit ? u->mcfg.dtype : u->cfg.dtype) == 1;       // (VAE / CLIP creators mirror dtype into cfg)
-  const bool f32 = !u->is_mmdit && u->cfg.dtype >= 2;                        // fp32-storage modes (SD-v1.4 UNet plans only)
-  const bool x3 = f32 && u->cfg.dtype == 3;                                  // ... with bf16x3 contractions (sdn_gemm_x3 / sdn_attention_x3)
+  const int sdt = u->is_mmdit ? u->mcfg.dtype : u->cfg.dtype;
+  const bool f32 = sdt >= 2;                                                 // fp32-storage modes (SD-v1.4 UNet, CLIP and MMDiT plans)
+  const bool x3 = f32 && sdt == 3;                                           // ... with bf16x3 contractions (sdn_gemm_x3 / sdn_attention_x3)
   for (const Op& o : p->ops) {
     int rc = SDN_OK;
     if (skip_text_kv && o.text_kv) { ++opi; continue; }       // its output of the previous forward stands (same text version)
@@ -1671,9 +1677,20 @@ static int launch_ops(sdn_unet* u, Plan* p, const char* W, const char* WS, const
                                                                          (float*)P(o.aux), stream);
           break;
         case OP_LN:
-          rc = o.mod ? SDN_E_INVALID
-                     : (o.tri_out ? sdn_layernorm_f32_triple : sdn_layernorm_f32)(P(o.a), o.rows, o.c1, o.eps, (const float*)P(o.w),
-                                                                                  (const float*)P(o.bias), (void*)P(o.out), stream);
+          if (o.mod) {                                 // MMDiT adaLN: w = scale, bias = shift (per-sample rows)
+            rc = o.tri_out ? SDN_E_INVALID
+                           : sdn_layernorm_mod_f32(P(o.a), o.rows, o.c1, o.eps, (const float*)P(o.w), (const float*)P(o.bias), o.ld_mod,
+                                                   o.hw, (void*)P(o.out), stream);
+            break;
+          }
+          rc = (o.tri_out ? sdn_layernorm_f32_triple : sdn_layernorm_f32)(P(o.a), o.rows, o.c1, o.eps, (const float*)P(o.w),
+                                                                          (const float*)P(o.bias), (void*)P(o.out), stream);
+          break;
+        case OP_PATCHIFY:
+          rc = sdn_patchify_f32((const float*)P(o.a), o.batch, o.c1, o.hw, o.hw, o.patch, (void*)P(o.out), stream);
+          break;
+        case OP_UNPATCHIFY:
+          rc = sdn_unpatchify_f32((const float*)P(o.a), o.batch, o.c1, o.hw, o.hw, o.patch, (float*)P(o.out), stream);
           break;
         case OP_ATTN:
           if (o.pair_in == 1) {                        // ld = 2 x (qkv width) bf16 elements, lo plane = one width on
@@ -1686,9 +1703,15 @@ static int launch_ops(sdn_unet* u, Plan* p, const char* W, const char* WS, const
                                         o.nq, o.nk, o.hd, 2 * o.ldq, 2 * o.ldk, 2 * o.ldv, o.ldo, o.scale, o.tri_out, stream);
             break;
           }
-          rc = o.n1 > 0 ? SDN_E_INVALID
-                        : (o.tri_out ? sdn_attention_x3_triple : (x3 ? sdn_attention_x3 : sdn_attention_f32))(
-                              P(o.a), P(o.k), P(o.v), (void*)P(o.out), o.batch, o.heads, o.nq, o.nk, o.hd, o.ldq, o.ldk, o.ldv, o.ldo, o.scale, stream);
+          if (o.n1 > 0) {                              // MMDiT joint attention over the image and text streams
+            sdn_attn_segment2 s2{P(o.q2), P(o.k2), P(o.v2), (void*)P(o.out2), o.n1, o.ldq, o.ldk, o.ldv, o.ldo};
+            rc = o.tri_out ? SDN_E_INVALID
+                           : sdn_joint_attention_f32(x3 ? 1 : 0, P(o.a), P(o.k), P(o.v), (void*)P(o.out), &s2, o.batch, o.heads, o.nq, o.hd,
+                                                     o.ldq, o.ldk, o.ldv, o.ldo, o.scale, stream);
+            break;
+          }
+          rc = (o.tri_out ? sdn_attention_x3_triple : (x3 ? sdn_attention_x3 : sdn_attention_f32))(
+              P(o.a), P(o.k), P(o.v), (void*)P(o.out), o.batch, o.heads, o.nq, o.nk, o.hd, o.ldq, o.ldk, o.ldv, o.ldo, o.scale, stream);
           break;
         case OP_REPEAT:
           rc = sdn_repeat(P(o.a), (size_t)o.rows, o.c1, (void*)P(o.out), stream);
@@ -1892,7 +1915,7 @@ static void drop_graphs(sdn_unet* u) {
 
 void sdn_unet_set_split_k(sdn_unet* u, int32_t on) {
   if (!u || u->split_k == (on != 0)) return;
-  if (!u->is_mmdit && !u->is_vae && u->cfg.dtype >= 2) return;   // fp32-storage modes have no split-K form
+  if (!u->is_vae && (u->is_mmdit ? u->mcfg.dtype : u->cfg.dtype) >= 2) return;   // fp32-storage modes have no split-K form
   u->split_k = on != 0;
   drop_graphs(u);
   u->plans.clear();                                            // plans are rebuilt with / without partial buffers

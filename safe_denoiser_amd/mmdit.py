@@ -20,12 +20,21 @@ SD3_MEDIUM = dict(in_channels=16, out_channels=16, sample_size=64, patch_size=2,
 
 class SD3Transformer2DModel(UNet2DConditionModel):
     """`sample_size` is the LATENT side this plan is built for (64 -> 512x512 images, the reference driver's default,
-    run_nudity_sdv3.py:357-358,500; 128 -> 1024x1024)."""
+    run_nudity_sdv3.py:357-358,500; 128 -> 1024x1024).
+    dtype=torch.float32 selects the fp32 precision plan (sdn_mmdit_config.dtype 2): weights, text, pooled projections and
+    activations stay f32 and the contractions run on the f32-input matrix cores.  precision = "bf16x3" (with dtype=torch.float32,
+    or alone) keeps the f32 storage and forms every contraction as three bf16 products (dtype 3, sdn_gemm_x3); "fp32" = dtype 2.
+    Same meaning as UNet2DConditionModel's arguments."""
 
-    def __init__(self, text_len: int = 333, dtype=torch.float16, **config):
-        if dtype not in (torch.bfloat16, torch.float16):
-            raise _lib.SdnError("storage dtype must be torch.bfloat16 or torch.float16")
+    def __init__(self, text_len: int = 333, dtype=torch.float16, precision: str | None = None, **config):
+        if precision not in (None, "fp32", "bf16x3"):
+            raise _lib.SdnError('precision must be None, "fp32" or "bf16x3"')
+        if precision is not None:
+            dtype = torch.float32                                   # both precision modes store f32
+        if dtype not in (torch.bfloat16, torch.float16, torch.float32):
+            raise _lib.SdnError("storage dtype must be torch.bfloat16, torch.float16 or torch.float32 (the precision mode)")
         self.dtype = dtype
+        self.precision = precision or ("fp32" if dtype == torch.float32 else None)
         cfg = dict(SD3_MEDIUM)
         cfg.update(config)
         self.config = SimpleNamespace(**cfg)
@@ -35,7 +44,8 @@ class SD3Transformer2DModel(UNet2DConditionModel):
                              sample_size=cfg["sample_size"], patch_size=cfg["patch_size"], num_layers=cfg["num_layers"],
                              num_heads=cfg["num_attention_heads"], head_dim=cfg["attention_head_dim"],
                              joint_dim=cfg["joint_attention_dim"], pooled_dim=cfg["pooled_projection_dim"],
-                             text_len=text_len, time_dim=256, dtype=0 if dtype == torch.bfloat16 else 1)
+                             text_len=text_len, time_dim=256,
+                             dtype=3 if self.precision == "bf16x3" else {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}[dtype])
         h = C.c_void_p()
         _lib.check(_lib.lib().sdn_mmdit_create(C.byref(c), C.byref(h)), "sdn_mmdit_create")
         self._h = h
@@ -84,6 +94,8 @@ class SD3Transformer2DModel(UNet2DConditionModel):
         return grid[top:top + hp, top:top + hp].reshape(hp * hp, -1)
 
     def pack_state_dict(self, sd: dict) -> torch.Tensor:
+        """CPU uint8 buffer in the engine layout: matrices (and the cropped position embedding) in the plan's storage dtype -- f32 in
+        the precision plans, like every bias and modulation vector."""
         buf = torch.zeros(self.weight_bytes, dtype=torch.uint8)
         for p in self.manifest:
             t = sd[p["name"]].detach().float().cpu()
@@ -106,10 +118,14 @@ class SD3Transformer2DModel(UNet2DConditionModel):
     def max_samples(self) -> int:
         """Largest batch ONE launch plan addresses (31-bit LDS-DMA offsets per operand): the widest 16-bit operand is the feed-forward
         hidden state, tokens x 4 x width x 2 B per sample -- 170 samples at 512^2, 42 at 1024^2 for SD3-medium.  `forward_into` runs
-        larger batches as consecutive row blocks (samples do not interact; one handle: this plan keeps no per-text cache)."""
+        larger batches as consecutive row blocks (samples do not interact; one handle: this plan keeps no per-text cache).
+        fp32-storage plans (precision "fp32" / "bf16x3"): the same rule at 4 B per element -- 85 samples at 512^2, 21 at 1024^2.  Their
+        kernels (sdn_gemm_f32 / sdn_gemm_x3, the f32 attention, LayerNorm, patchify and unpatchify) address every operand with 64-bit
+        element offsets, so the cap keeps each operand under 2 GiB as a margin, not because a kernel would wrap."""
         c = self.config
         tokens = (c.sample_size // c.patch_size) ** 2
-        return ((1 << 31) - 1) // (tokens * 4 * c.num_attention_heads * c.attention_head_dim * 2)
+        esz = 4 if self.precision in ("fp32", "bf16x3") else 2
+        return ((1 << 31) - 1) // (tokens * 4 * c.num_attention_heads * c.attention_head_dim * esz)
 
     def forward_into(self, sample, timestep, text16, pooled16, out):
         b = sample.shape[0]

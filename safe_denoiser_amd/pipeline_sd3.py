@@ -38,6 +38,7 @@ from typing import Callable, Optional
 import torch
 
 from . import _lib
+from .pipeline import SafeDenoiserPipeline
 
 
 class StableDiffusion3PipelineOutput:
@@ -55,8 +56,18 @@ SD3_NEGATIVE_PROMPT_SPACE = ["Sexual Acts", "Content Meant to Arouse Sexual Exci
 
 
 class SD3SafeDenoiserPipeline:
-    def __init__(self, transformer, scheduler, vae=None, text_front_end=None):
+    def __init__(self, transformer, scheduler, vae=None, text_front_end=None, transformer_hi=None, precision_schedule=None):
         self.transformer, self.scheduler, self.vae = transformer, scheduler, vae
+        # Precision schedule, as SafeDenoiserPipeline's `unet_hi` / `precision_schedule`: `transformer_hi` is a second plan over the
+        # same weights in a precision mode (SD3Transformer2DModel(precision="bf16x3" | "fp32")) and `precision_schedule` says which
+        # steps run on it (the forms of SafeDenoiserPipeline.hi_steps; "window" = the flow-repellency window, 780 <= t <= 1000 with a
+        # processor).  Every other step runs on `transformer`.  No default schedule.
+        self.transformer_hi, self.precision_schedule = transformer_hi, precision_schedule
+        if (transformer_hi is None) != (precision_schedule is None):
+            raise _lib.SdnError("transformer_hi and precision_schedule go together")
+        if transformer_hi is not None and (vars(transformer.config) != vars(transformer_hi.config)
+                                           or transformer.text_len != transformer_hi.text_len):
+            raise _lib.SdnError("transformer_hi must be the same architecture / text_len as transformer")
         self.text_front_end = text_front_end   # the caller's CLIP x2 + T5 stack (see the module docstring); None = embeddings only
         self.vae_scale_factor = 8
         self.last_stats = {}
@@ -128,13 +139,20 @@ class SD3SafeDenoiserPipeline:
                             ["rescaled_text_embeddings"][1])
             rescaled_text_embeddings = torch.cat([E[:P], torch.stack(rows).to(E.dtype)])
         text_src = prompt_embeds if rescaled_text_embeddings is None else rescaled_text_embeddings
-        text = tr.prepare_text(text_src.to(dev))
-        pooled = pooled_prompt_embeds.to(device=dev, dtype=tr.dtype).contiguous()
+        nets = [tr] if self.transformer_hi is None else [tr, self.transformer_hi]
+        text_of, pooled_of = {}, {}                                           # each plan reads text / pooled in its own storage dtype
+        for net in nets:
+            if net.dtype not in text_of:
+                text_of[net.dtype] = net.prepare_text(text_src.to(dev))
+                pooled_of[net.dtype] = pooled_prompt_embeds.to(device=dev, dtype=net.dtype).contiguous()
 
         sch = self.scheduler
         sch.set_timesteps(num_inference_steps)
         ts = [float(t) for t in sch._ts_host]
         sig_step = [float(x) for x in sch._sig_host]                         # Euler grid (sigma_n = 0 appended)
+        # steps on transformer_hi; without a processor the loop has no repellency window, so {"window": True} selects none
+        use_hi = (self.hi_steps(ts, "t" if repellency_processor is not None else "no window", lo, hi)
+                  if self.transformer_hi is not None else [False] * len(ts))
 
         def rq(x):                                                            # latents.to(latents_dtype) round trip
             return x if latents_dtype == torch.float32 else x.to(latents_dtype).float()
@@ -182,7 +200,8 @@ class SD3SafeDenoiserPipeline:
         n_win = 0
         for i, t in enumerate(ts):
             x_in.view(2, P, C_, s, s).copy_(cur)
-            tr.forward_into(x_in, t, text, pooled, vout)
+            net = self.transformer_hi if use_hi[i] else tr
+            net.forward_into(x_in, t, text_of[net.dtype], pooled_of[net.dtype], vout)
             vq = vout if latents_dtype == torch.float32 else vout.to(latents_dtype).float()   # model output is fp16 in the ref
             _lib.check(L.sdn_cfg_combine(vq.data_ptr(), P, 2, D, float(guidance_scale), v.data_ptr(), st), "sdn_cfg_combine")
             if lo <= t <= hi and repellency_processor is not None:
@@ -211,7 +230,7 @@ class SD3SafeDenoiserPipeline:
             rq_(nxt)
             cur, nxt = nxt, cur
         lat = cur.clone()                                                       # the loop buffers are reused by the next call
-        self.last_stats = {"window_steps": n_win, "prompts": P}
+        self.last_stats = {"window_steps": n_win, "prompts": P, "hi_steps": int(sum(use_hi))}
         wrap = (lambda im: StableDiffusion3PipelineOutput(im) if return_dict else (im,))
         if return_latents:
             return wrap(lat.to(latents_dtype)) if output_type == "latent" else lat.to(latents_dtype)
@@ -224,3 +243,7 @@ class SD3SafeDenoiserPipeline:
             from PIL import Image
             image = [Image.fromarray(im) for im in (image * 255).round().astype("uint8")]
         return wrap(image)
+
+    # the schedule forms of the SD-v1.4 pipeline (sequence, callable (i, t, in_window), dict of first / last / window / steps, "all",
+    # "none"); `kind` "t" = the window is lo <= t <= hi, any other value = no window
+    hi_steps = SafeDenoiserPipeline.hi_steps
