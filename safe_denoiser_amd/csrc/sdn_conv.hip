@@ -259,6 +259,7 @@ k_conv_slab(const GemmArgs g) {
 template <typename T>
 static int launch_slab(const GemmArgs& g, hipStream_t st) {
   const int grid = g.tiles_m * g.tiles_n;
+  if (g.Ws == 64 || g.Ws == 32 || g.Ws == 16) record_gemm_launch(2, T::kDtype, 10, 4, 2, 0, g.tiles_m, g.tiles_n, 1, g.Ws);
   switch (g.Ws) {
     case 64: hipLaunchKernelGGL((k_conv_slab<T, 64>), dim3(grid), dim3(512), 0, st, g); break;
     case 32: hipLaunchKernelGGL((k_conv_slab<T, 32>), dim3(grid), dim3(512), 0, st, g); break;

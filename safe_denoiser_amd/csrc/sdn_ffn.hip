@@ -356,6 +356,7 @@ extern "C" int sdn_ffn_geglu_fused(int32_t dtype, int64_t M, int32_t C, const vo
   if (M == 0) return SDN_OK;
   FfnArgs a{x, row_stats, w1_folded, c1, d1, w_cat, b_cat, residual, out, col_stats, (int)M};
   const unsigned grid = (unsigned)((M + 127) / 128);
+  record_gemm_launch(4, dtype, 10, 2, 2, row_stats ? 2 : 1, (int)grid, 1, 1, 0);
   if (dtype == 1) hipLaunchKernelGGL((k_ffn320<SdnF16>), dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL((k_ffn320<SdnBF16>), dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
   return sdn_launch_status();

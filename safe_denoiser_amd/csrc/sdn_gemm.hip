@@ -579,6 +579,7 @@ template <typename T, int NREP, int WGM, int NSTAGE = 2, int LNF = 0>
 int launch_dma(const GemmArgs& ga, hipStream_t st) {
   const int grid = ga.tiles_m * ga.tiles_n;
   const int splits = ga.kt_per_split > 0 ? (ga.K / BK + ga.kt_per_split - 1) / ga.kt_per_split : 1;
+  record_gemm_launch(ga.kt_per_split > 0 ? 3 : 1, T::kDtype, NREP, WGM, NSTAGE, LNF, ga.tiles_m, ga.tiles_n, splits, 0);
   hipLaunchKernelGGL((k_gemm_dma<T, NREP, WGM, NSTAGE, LNF>), dim3(grid, splits), dim3(128 * WGM), 0, st, ga);
   return sdn_launch_status();
 }
@@ -652,6 +653,17 @@ extern "C" void sdn_debug_gemm_launch_counts(long long* out2, int reset) {
   if (reset) g_gemm_launches[0] = g_gemm_launches[1] = 0;
 }
 extern "C" void sdn_debug_set_gemm_stamps(void* p) { g_gemm_stamps = (unsigned long long*)p; }
+// diagnostics (tests): the instantiation the last GEMM-family launch ran -- family, dtype, NREP, WGM, NSTAGE, LNF, tiles_m, tiles_n,
+// splits, aux (see record_gemm_launch) -- so that a test written for one instantiation notices when the tile heuristic moves it
+static int g_last_launch[SDN_LL_COUNT] = {0};
+void sdn_gemm_detail::record_gemm_launch(int family, int dtype, int nrep, int wgm, int nstage, int lnf, int tiles_m, int tiles_n,
+                                         int splits, int aux) {
+  const int v[SDN_LL_COUNT] = {family, dtype, nrep, wgm, nstage, lnf, tiles_m, tiles_n, splits, aux};
+  for (int i = 0; i < SDN_LL_COUNT; ++i) g_last_launch[i] = v[i];
+}
+extern "C" void sdn_debug_gemm_last_launch(int* out, int n) {
+  for (int i = 0; out && i < n; ++i) out[i] = i < SDN_LL_COUNT ? g_last_launch[i] : 0;
+}
 
 // Tile choice with the grid in mind: when the widest tile leaves the 256 CUs (x2 resident blocks) underfilled
 // (the 8x8 / 16x16 levels at small batch), fall back to BN = 64 to multiply the number of workgroups.

@@ -5,11 +5,20 @@ import torch
 
 import safe_denoiser_amd as sda
 from safe_denoiser_amd import _lib
+from tests_support.exact import sentinel_fill
 
 BF = torch.bfloat16
 
 
 X3 = False      # tests of the bf16x3 contraction mode set this: f32 tensors then go to sdn_gemm_x3 / sdn_attention_x3
+
+SENTINEL = False    # tests set this: GEMM outputs start as a NaN bit pattern (exact.sentinel_fill) instead of torch.empty, so that
+                    # a tile a kernel never writes cannot pass by inheriting a previous call's identical result from the allocator
+
+
+def _out(shape, dtype, device):
+    t = torch.empty(shape, dtype=dtype, device=device)
+    return sentinel_fill(t) if SENTINEL else t
 
 
 def _fn(base: str, t: torch.Tensor):
@@ -21,8 +30,9 @@ def _fn(base: str, t: torch.Tensor):
 
 
 def gemm(a, w, *, bias=None, rowbias=None, residual=None, a2=None, conv=None, act=0, out_kind=0, n_valid=0,
-         rows_per_batch=0, rowgate=None, residual_bcast=0, split_k=0, col_stats=None, res_pre=0):
-    """a [M,K] bf16 (or NHWC map for conv=dict(Hs,Ws,Cin,Ho,Wo,stride,upsample)), w [N,K] bf16."""
+         rows_per_batch=0, rowgate=None, residual_bcast=0, split_k=0, col_stats=None, res_pre=0, out=None):
+    """a [M,K] bf16 (or NHWC map for conv=dict(Hs,Ws,Cin,Ho,Wo,stride,upsample)), w [N,K] bf16.
+    out: a caller-owned output (e.g. a view into a guarded buffer); its row stride becomes ldc."""
     N, K = w.shape
     d = _lib.GemmDesc()
     if conv:
@@ -45,12 +55,15 @@ def gemm(a, w, *, bias=None, rowbias=None, residual=None, a2=None, conv=None, ac
         d.ld_rowgate = rowgate.stride(0)
     d.residual_bcast = residual_bcast
     nv = n_valid or N
-    if out_kind == 0:
-        out = torch.empty((M, N // 2 if act == 2 else nv), dtype=a.dtype, device=a.device)
+    if out is not None:
+        if out_kind != 2:
+            d.ldc = out.stride(0)
+    elif out_kind == 0:
+        out = _out((M, N // 2 if act == 2 else nv), a.dtype, a.device)
     elif out_kind == 1:
-        out = torch.empty((M, nv), dtype=torch.float32, device=a.device)
+        out = _out((M, nv), torch.float32, a.device)
     else:
-        out = torch.empty((M // rows_per_batch, nv, rows_per_batch), dtype=torch.float32, device=a.device)
+        out = _out((M // rows_per_batch, nv, rows_per_batch), torch.float32, a.device)
     p = lambda t: None if t is None else t.data_ptr()
     if col_stats is not None:
         _lib.check(_fn("gemm_stats", a)(C.byref(d), p(a), p(a2), p(w), p(bias), p(rowbias), p(residual), p(out), p(col_stats),
@@ -104,9 +117,10 @@ def attention(q, k, v, heads, scale=None):
     return out
 
 
-def gemm_ln(x, w, gamma, beta, bias=None, act=0, eps=1e-5, prepass=False):
+def gemm_ln(x, w, gamma, beta, bias=None, act=0, eps=1e-5, prepass=False, out=None, fold=None):
     """LayerNorm(x; gamma, beta) . w^T + bias [GEGLU] through sdn_ln_fold + sdn_gemm_ln_* (w [N, K] 16-bit, already in the
-    layout the kernel expects -- interleaved for GEGLU)."""
+    layout the kernel expects -- interleaved for GEGLU).  out: caller-owned output (row stride = ldc); fold: a dict that
+    receives the folded operands the GEMM ran on (w_folded, c, d)."""
     N, K = w.shape
     M = x.shape[0]
     code = 1 if x.dtype == torch.float16 else 0
@@ -116,7 +130,12 @@ def gemm_ln(x, w, gamma, beta, bias=None, act=0, eps=1e-5, prepass=False):
     _lib.check(sda.lib().sdn_ln_fold(code, p(w), p(gamma), p(beta), p(bias), N, K, p(wf), p(c), p(dv), _lib.stream_ptr()), "sdn_ln_fold")
     d = _lib.GemmDesc()
     d.M, d.N, d.K, d.act = M, N, K, act
-    out = torch.empty((M, N // 2 if act == 2 else N), dtype=x.dtype, device=x.device)
+    if fold is not None:
+        fold.update(w_folded=wf, c=c, d=dv)
+    if out is None:
+        out = _out((M, N // 2 if act == 2 else N), x.dtype, x.device)
+    else:
+        d.ldc = out.stride(0)
     stats = None
     if prepass:
         stats = torch.empty(M, 2, dtype=torch.float32, device=x.device)
@@ -139,7 +158,7 @@ def ffn_fused(x, w1, gamma, beta, bias1, w_cat, b_cat, residual, col_stats=None,
     if not own_stats:
         stats = torch.empty(M, 2, dtype=torch.float32, device=x.device)
         _lib.check(_fn("row_stats", x)(p(x), M, K, eps, p(stats), _lib.stream_ptr()), "sdn_row_stats")
-    out = torch.empty((M, K), dtype=x.dtype, device=x.device)
+    out = _out((M, K), x.dtype, x.device)
     _lib.check(sda.lib().sdn_ffn_geglu_fused(code, M, K, p(x), p(stats), p(wf), p(c), p(dv), p(w_cat), p(b_cat), p(residual), p(out),
                                              p(col_stats), _lib.stream_ptr()), "sdn_ffn_geglu_fused")
     return out
