@@ -184,6 +184,8 @@ int sdn_flow_renoise(const float* x0r, const float* x1, const float* z, int64_t 
 #define SDN_ACT_GEGLU  2   /* W rows interleaved value/gate in blocks of 16; out = v*gelu(g)  */
 #define SDN_ACT_GELU_TANH 3 /* GELU(approximate="tanh") -- MMDiT feed-forward                   */
 #define SDN_ACT_QUICK_GELU 4 /* x * sigmoid(1.702 x) -- CLIP text encoder MLP                     */
+#define SDN_ACT_GEGLU_TANH 5 /* the layout of SDN_ACT_GEGLU with out = v * gelu_tanh(g): T5 gated-gelu (gelu_new(wi_0 x) * wi_1 x,
+                               value rows = wi_1, gate rows = wi_0); plain sdn_gemm_bf16 / sdn_gemm_f16 only             */
 #define SDN_OUT_BF16      0   /* [M, ldc] bf16                                                */
 #define SDN_OUT_F32       1   /* [M, ldc] f32                                                 */
 #define SDN_OUT_F32_NCHW  2   /* [B, n_valid, rows_per_batch] f32 (conv_out -> latent layout) */
@@ -222,6 +224,9 @@ typedef struct sdn_gemm_desc {
                                matrix instruction, f32 accumulation throughout (1.2e-5 ... 2.2e-5 from float64 per
                                GEMM against fp16's 2.9e-4 and bf16x3's 4.5e-6).  256-row tiles only (N % 256 == 0 or N % 320 == 0
                                with >= 192 tiles); not used by any plan yet                                                   */
+  int32_t f32_stream;       /* 1 = sdn_gemm_bf16 / sdn_gemm_f16 over ordinary 16-bit operands (plain A, no activation, no gate, x3_out 0,
+                               out_kind SDN_OUT_F32): `residual` is F32 [M, ldc] (may alias out) and out is F32 [M, ldc], straight from
+                               the accumulators -- the f32 residual stream of the T5 plan, fed by 16-bit projections          */
 } sdn_gemm_desc;
 
 /* out = act((A.W^T + bias[n] + rowbias[b(m), n]) * rowgate[b(m), n] + residual[m, n])   (rowgate NULL = 1).
@@ -444,6 +449,10 @@ typedef struct sdn_unet sdn_unet;   /* opaque: op plan + parameter manifest (hos
 #define SDN_P_GEGLU_MAT   3   /* [2F,in] -> bf16, rows interleaved value/gate in blocks of 16  */
 #define SDN_P_GEGLU_VEC   4   /* [2F] -> f32, interleaved the same way                         */
 #define SDN_P_POS_CROP    5   /* [1, max*max, C] -> 16-bit [h*w, C], centre crop (MMDiT pos_embed) */
+#define SDN_P_GLU_VALUE   7   /* [F,in] -> 16-bit: the VALUE rows of an SDN_ACT_GEGLU* weight whose gate is a separate
+                                 state_dict tensor (T5 wi_1): source rows [16 b, 16 b + 16) go to packed rows [32 b, 32 b + 16)
+                                 from `offset` on (row stride = cols elements) */
+#define SDN_P_GLU_GATE    8   /* ... and its GATE rows (T5 wi_0): same mapping; `offset` already points 16 rows into the pair */
 #define SDN_P_DERIVED     6   /* not a state_dict tensor: `rows` BYTES the engine fills itself from other entries
                                  (LayerNorm-folded weights); loaders skip it and call sdn_unet_prepare afterwards */
 
@@ -638,6 +647,57 @@ int sdn_clip_embed_f32(const int32_t* input_ids, const void* token_embedding, co
 int sdn_masked_attention_f32(const void* q, const void* k, const void* v, void* out, const int32_t* key_mask, int32_t causal,
                              int32_t batch, int32_t heads, int32_t n, int32_t head_dim, int32_t ldq, int32_t ldk, int32_t ldv,
                              int32_t ldo, float scale, void* stream);
+
+/* ---- T5 encoder (SD-v3 text_encoder_3: the encoder every SD-v3 SAFREE decision rests on) ---------------------------------
+ * Replaces `self.text_encoder_3(input_ids, attention_mask=...)[0]` (transformers T5EncoderModel, third party), called at
+ * models/sdv3/safe_denoiser_pipeline.py:316-334 (prompt embeddings), :731-768 (concept phrases) and :797-827 (one sequence per
+ * real token).  Handle = sdn_unet; manifest and weights through the sdn_unet_* queries.  Manifest keys are T5EncoderModel's
+ * without the `encoder.` prefix: embed_tokens.weight, block.N.layer.0.{SelfAttention.{q,k,v,o}.weight,layer_norm.weight},
+ * block.0.layer.0.SelfAttention.relative_attention_bias.weight, block.N.layer.1.{DenseReluDense.{wi_0,wi_1,wo}.weight,
+ * layer_norm.weight}, final_layer_norm.weight.  No biases anywhere.  The residual stream is F32 between sublayers (the 16-bit
+ * projections add into it: sdn_gemm_desc.f32_stream), so neither transformers' fp16 clamping nor its fp32 `wo` is needed. */
+typedef struct sdn_t5_config {
+  int32_t vocab_size;                    /* 32128                                                      */
+  int32_t d_model, d_kv, d_ff;           /* 4096, 64 (must be 64), 10240                               */
+  int32_t num_layers, num_heads;         /* 24, 64 (num_heads * d_kv need not equal d_model)           */
+  int32_t num_buckets, max_distance;     /* 32, 128: relative_attention_num_buckets / _max_distance    */
+  float   eps;                           /* 1e-6                                                       */
+  int32_t dtype;                         /* 0 = bf16, 1 = fp16 storage; 2 / 3 (fp32 storage) are refused for now */
+} sdn_t5_config;
+int sdn_t5_create(const sdn_t5_config* cfg_host, sdn_unet** out_host);
+/* The sequence length is a CALL-TIME argument (2 <= n <= 512): the masked-token call pads to the prompt's own length.  Plans are
+ * cached per (batch, n); the handle keeps no "current" length.  The generic queries sdn_unet_workspace_bytes(t5, batch) and
+ * sdn_unet_flops(t5, batch, ..) answer for n = 512 (the workspace bound of any n); these two answer for a given n.
+ * sdn_unet_set_split_k and graph mode do not apply to a T5 handle. */
+size_t sdn_t5_workspace_bytes(sdn_unet* t5, int32_t batch, int32_t n);
+double sdn_t5_flops(sdn_unet* t5, int32_t batch, int32_t n, double* attention_core_flops_host);
+/* out [B, n, d_model] (16-bit, after final_layer_norm) = encoder(input_ids [B, n] int32, attention_mask [B, n] int32 with
+ * 1 = attend / 0 = padding key, or NULL).  Ids outside the vocabulary are clamped. */
+int sdn_t5_forward(sdn_unet* t5, const void* weights, const int32_t* input_ids, const int32_t* attention_mask, int32_t n,
+                   void* out, int32_t batch, void* workspace, size_t workspace_bytes, void* stream);
+/* its building blocks (dtype 0 = bf16, 1 = fp16):
+ * sdn_rmsnorm: T5LayerNorm, out = x * rsqrt(mean(x^2) + eps) * weight -- no mean subtraction, no bias, statistics in f32; x is
+ *   [rows, c] f32 (x_is_f32 = 1) or 16-bit, out 16-bit, weight f32; c % 4 == 0.
+ * sdn_embed_tokens: out [rows, hidden] F32 = table[ids] (16-bit table, no position table).
+ * sdn_t5_relative_bias: out [heads, 2 n - 1] F32, out[h, (j - i) + n - 1] = table[bucket(j - i), h] for key j and query i, from the
+ *   16-bit table [num_buckets, heads] (block 0's relative_attention_bias.weight); bidirectional bucketing.  The bias is Toeplitz,
+ *   so this vector IS the whole operand: [heads, n, n] is never materialised.  sdn_t5_bucket is the (host) bucket function: it
+ *   evaluates transformers' float32 formula with the host's logf and is verified against transformers, at every distance, for
+ *   (32 buckets, max distance 128) -- the pair every T5-v1.1 checkpoint uses -- ONLY; at another pair a one-ulp difference between
+ *   the two logarithms at a bucket edge could move that edge by one position.
+ * sdn_bias_attention: softmax(scale Q K^T + bias[h, j - i] + key mask) V, bidirectional, head_dim 64, 2 <= n <= 512; q / k / v / out
+ *   and key_mask [B, n] (nullable) as in sdn_masked_attention; bias as written by sdn_t5_relative_bias.  Running-maximum softmax in
+ *   both dtypes: finite for any finite scores. */
+int sdn_rmsnorm(int32_t dtype, const void* x, int32_t x_is_f32, int64_t rows, int32_t c, float eps, const float* weight, void* out,
+                void* stream);
+int sdn_embed_tokens(int32_t dtype, const int32_t* input_ids, const void* token_embedding, int64_t rows, int32_t hidden,
+                     int32_t vocab, float* out, void* stream);
+int sdn_t5_bucket(int32_t relative_position, int32_t num_buckets, int32_t max_distance);
+int sdn_t5_relative_bias(int32_t dtype, const void* table, int32_t num_buckets, int32_t max_distance, int32_t heads, int32_t n,
+                         float* out, void* stream);
+int sdn_bias_attention(int32_t dtype, const void* q, const void* k, const void* v, void* out, const float* bias,
+                       const int32_t* key_mask, int32_t batch, int32_t heads, int32_t n, int32_t head_dim, int32_t ldq,
+                       int32_t ldk, int32_t ldv, int32_t ldo, float scale, void* stream);
 
 /* Text K / V reuse across the steps of a denoising loop.  The cross-attention key / value projections (16 per forward) read only
  * `text`, which the reference's loop feeds unchanged for all but a few of its 50 steps (the SAFREE-projected embeddings for the

@@ -35,7 +35,8 @@ class RepelParams(C.Structure):
 class GemmDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("M", "N", "K", "a_mode", "K1", "Hs", "Ws", "Cin", "Ho", "Wo", "stride",
                                          "upsample", "act", "out_kind", "rows_per_batch", "ld_rowbias", "ld_rowgate",
-                                         "residual_bcast", "n_valid", "ldc", "asym_pad", "split_k", "res_pre", "x3_out")]
+                                         "residual_bcast", "n_valid", "ldc", "asym_pad", "split_k", "res_pre", "x3_out",
+                                         "f32_stream")]
 
 
 class UnetConfig(C.Structure):
@@ -65,6 +66,11 @@ class VaeConfig(C.Structure):
 class ClipConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("vocab_size", "hidden_size", "intermediate_size", "num_layers", "num_heads",
                                          "max_position_embeddings", "dtype")]
+
+
+class T5Config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("vocab_size", "d_model", "d_kv", "d_ff", "num_layers", "num_heads", "num_buckets",
+                                         "max_distance")] + [("eps", C.c_float), ("dtype", C.c_int32)]
 
 
 class AttnSegment2(C.Structure):
@@ -170,6 +176,16 @@ SIGNATURES = {
     "sdn_clip_embed": (C.c_int, [_i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "sdn_masked_attention": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                        _f32, _vp]),
+    "sdn_t5_create": (C.c_int, [C.POINTER(T5Config), C.POINTER(_vp)]),
+    "sdn_t5_workspace_bytes": (_sz, [_vp, _i32, _i32]),
+    "sdn_t5_flops": (C.c_double, [_vp, _i32, _i32, C.POINTER(C.c_double)]),
+    "sdn_t5_forward": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _sz, _vp]),
+    "sdn_rmsnorm": (C.c_int, [_i32, _vp, _i32, _i64, _i32, _f32, _vp, _vp, _vp]),
+    "sdn_embed_tokens": (C.c_int, [_i32, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "sdn_t5_bucket": (C.c_int, [_i32, _i32, _i32]),
+    "sdn_t5_relative_bias": (C.c_int, [_i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "sdn_bias_attention": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32,
+                                     _vp]),
     "sdn_split3": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "sdn_expand3_weights": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp]),
     "sdn_groupnorm_f32_triple": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),

@@ -41,8 +41,39 @@ def find_weights(component_dir: str, variant: Optional[str] = None) -> str:
     raise FileNotFoundError(f"no weight file in {component_dir} (looked for {', '.join(names)})")
 
 
+def find_index(component_dir: str, variant: Optional[str] = None) -> Optional[str]:
+    """The shard index of a component whose weights are split over several safetensors files; None for a single file."""
+    names = ("model.safetensors.index.json", "diffusion_pytorch_model.safetensors.index.json")
+    if variant:
+        names = tuple(n.replace(".index.json", f".index.{variant}.json") for n in names) + names
+    for n in names:
+        p = os.path.join(component_dir, n)
+        if os.path.isfile(p):
+            return p
+    return None
+
+
 def load_weights(component_dir: str, variant: Optional[str] = None) -> dict:
-    """diffusers-keyed state_dict of one component, as CPU tensors."""
+    """diffusers-keyed state_dict of one component, as CPU tensors.  A sharded component (`*.safetensors.index.json` with a
+    `weight_map`, as SD-v3's two-shard text_encoder_3) is read shard by shard into one dict."""
+    index = find_index(component_dir, variant)
+    if index is not None:
+        from safetensors.torch import load_file
+        with open(index) as f:
+            weight_map = json.load(f).get("weight_map")
+        if not isinstance(weight_map, dict) or not weight_map:
+            raise ValueError(f"{index}: no weight_map")
+        sd = {}
+        for shard in sorted(set(weight_map.values())):
+            sp = os.path.join(component_dir, shard)
+            if not os.path.isfile(sp):
+                raise FileNotFoundError(f"{sp}: shard named by {os.path.basename(index)} is missing")
+            part = load_file(sp, device="cpu")
+            sd.update({k: v for k, v in part.items() if weight_map.get(k) == shard})
+        missing = [k for k in weight_map if k not in sd]
+        if missing:
+            raise KeyError(f"{index}: {len(missing)} tensors of the weight_map are in no shard, e.g. {missing[:3]}")
+        return sd
     path = find_weights(component_dir, variant)
     if path.endswith(".safetensors"):
         from safetensors.torch import load_file
@@ -90,6 +121,23 @@ def vae_kwargs(cfg: dict) -> dict:
 def clip_kwargs(cfg: dict) -> dict:
     _require(cfg, "text_encoder", hidden_act="quick_gelu")
     keys = ("vocab_size", "hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "max_position_embeddings")
+    return {k: cfg[k] for k in keys if k in cfg}
+
+
+def t5_kwargs(cfg: dict) -> dict:
+    """T5EncoderModel(**kwargs) from text_encoder_3/config.json (T5-v1.1 family, encoder-only use)."""
+    if cfg.get("feed_forward_proj") != "gated-gelu":
+        raise NotImplementedError(f"text_encoder_3: feed_forward_proj = {cfg.get('feed_forward_proj')!r} is not implemented by the "
+                                  "engine's plan (needs 'gated-gelu')")
+    if cfg.get("d_kv") != 64:
+        raise NotImplementedError(f"text_encoder_3: d_kv = {cfg.get('d_kv')!r} is not implemented by the engine's plan (needs 64)")
+    arch = cfg.get("architectures")
+    if cfg.get("is_decoder") or (arch is not None and list(arch) != ["T5EncoderModel"]):
+        raise NotImplementedError(f"text_encoder_3: only the encoder-only use (architectures = ['T5EncoderModel']) is implemented, "
+                                  f"got architectures = {arch!r}, is_decoder = {cfg.get('is_decoder')!r}")
+    _require(cfg, "text_encoder_3", dense_act_fn="gelu_new", is_gated_act=True)
+    keys = ("vocab_size", "d_model", "d_kv", "d_ff", "num_layers", "num_heads", "relative_attention_num_buckets",
+            "relative_attention_max_distance", "layer_norm_epsilon")
     return {k: cfg[k] for k in keys if k in cfg}
 
 

@@ -77,6 +77,7 @@ struct AttnArgs {
   int head_inner;                    // block order for short key sets, see the block-index decode
   int causal; const int* kmask;      // MASK instantiation only: key <= query; kmask [B, nk] (0 = padded key), nullable
   int nomax;                         // bf16: first pass without the per-tile running maximum (see "optimistic pass"); 0 = guarded pass only
+  const float* bias;                 // BIAS instantiation only: per-head Toeplitz score bias [heads, 2 nk - 1], natural-log units
 };
 
 // Row `row` of sample b in a (possibly two-segment) [B, n, ld] tensor.
@@ -93,7 +94,10 @@ __device__ __forceinline__ const unsigned short* row_ptr(const unsigned short* p
 // MFMAs, halving the LDS bytes per FLOP, and the softmax VALU of one set can issue under the MFMAs of the other inside ONE
 // wave -- the d = 40 loop is bound by vector issue + LDS + matrix pipe all at ~60 %, at a clock the chip holds
 // down; less LDS traffic per MFMA is the lever that raises it.  Costs registers: 2 waves per SIMD instead of 4.
-template <typename T, int HD, bool SEG, bool MASK = false, bool DMA = !SEG, int QS = 1>
+// BIAS (T5 self-attention): scores = scale Q K^T + bias[head, key - query], a Toeplitz bias held as one vector per head in LDS.
+// T5 scores are not scaled by 1 / sqrt(d) and trained biases reach tens, so neither the offset-free bf16 form nor the fp16 form
+// centred on the first tile is sound here: both dtypes take the classic running-maximum loop (as every masked fp16 instance does).
+template <typename T, int HD, bool SEG, bool MASK = false, bool DMA = !SEG, int QS = 1, bool BIAS = false>
 __global__ void __launch_bounds__(THREADS)
 k_attn(const AttnArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -101,7 +105,8 @@ k_attn(const AttnArgs a) {
   constexpr int KQ = (HD + 15) / 16;          // 16-deep k-steps of Q K^T
   constexpr int NDB = (HD + 31) / 32;         // 32-row blocks of O^T
   constexpr bool ONES = (HD % 32) != 0;       // a free padding column exists -> row sums via MFMA
-  constexpr bool OFFSET_FREE = T::kDtype == 0; // bf16 has fp32's exponent range: softmax without max subtraction (below)
+  static_assert(!BIAS || (MASK && DMA && QS == 1), "the biased form extends the masked single-buffer instance");
+  constexpr bool OFFSET_FREE = T::kDtype == 0 && !BIAS; // bf16 has fp32's exponent range: softmax without max subtraction (below)
   // fp16 with a FREE padding column in the Q K^T contraction (d = 40 -> 48) and LDS-DMA tiles -- round 5.  fp16's P needs p < 2^16,
   // so the bf16 form (no offset at all) is out; the classic form pays one FMA + 1/2 v_max3 per score that the bf16 loop does not
   // (VALU is this kernel's bound: 31.4 vs 23.5 ms per forward at B = 192).  Here the scale is folded into Q as for bf16 and the
@@ -139,7 +144,8 @@ k_attn(const AttnArgs a) {
   constexpr int STAGE = KV * KSTR + KV * VSTR;
   constexpr int ZOFF = 2 * STAGE;             // static block: [1,0,0,0 | 0,0,0,0 | 0 x 8] (16-bit), DMA mode only
   constexpr int NLOAD = (2 * KV * CH + THREADS - 1) / THREADS;   // staged chunks per thread per tile (register staging)
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * STAGE + 48];          // + static block (32 B) + the re-run flag
+  constexpr int BOFF = ZOFF + 64;             // BIAS: this head's bias vector, 2 nk - 1 <= 1023 floats, pre-multiplied by log2(e)
+  __shared__ __attribute__((aligned(1024))) unsigned char smem[BIAS ? BOFF + 4096 : 2 * STAGE + 48];   // + static block (32 B) + the re-run flag
 
   // K/V tile DMA of the next tile: at the top of the iteration, or (d = 40: +1.5-3 %; d = 80 / 160 lose 3-6 %) after the QK^T MFMAs
   constexpr bool kLateDma = HD == 40;
@@ -190,6 +196,12 @@ k_attn(const AttnArgs a) {
       for (int c = CH * 16; c < KQ * 32; c += 4) *reinterpret_cast<unsigned*>(sK + c) = 0u;
       for (int c = CH * 16; c < NDB * 64; c += 4) *reinterpret_cast<unsigned*>(sV + c) = (ONES && c == CH * 16) ? one16 : 0u;
     }
+  }
+
+  if constexpr (BIAS) {                          // (published by the barrier in front of the first tile)
+    const int L = 2 * a.nk - 1;
+    for (int e = tid; e < L; e += THREADS)
+      reinterpret_cast<float*>(smem + BOFF)[e] = a.bias[(long)head * L + e] * 1.4426950408889634f;
   }
 
   // ---- Q fragments (B operand: lane (r,h) holds Q[q0+r][16s + 8h .. +8)) ----
@@ -398,6 +410,21 @@ k_attn(const AttnArgs a) {
     }
     __builtin_amdgcn_s_setprio(0);
     if constexpr (DMA && kLateDma) { if (t + 1 < ntiles) dma_issue(buf ^ 1, t + 1); }   // behind the QK^T MFMAs already in the pipe
+    if constexpr (BIAS) {                         // s = c q.k + log2(e) bias[key - query]: from here on the scores are in log2 units
+      const float* sb = reinterpret_cast<const float*>(smem + BOFF);
+      const int k0 = t * KV, last = 2 * a.nk - 2;
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int key = k0 + 32 * kb + (i & 3) + 8 * (i >> 2) + 4 * h;
+#pragma unroll
+          for (int qs = 0; qs < QS; ++qs) {
+            const int idx = key - (q0 + 32 * qs + r) + a.nk - 1;           // (clamped for the key / query tails, which are masked / not stored)
+            st[qs][kb][i] = fmaf(st[qs][kb][i], a.c, sb[min(max(idx, 0), last)]);
+          }
+        }
+    }
     if constexpr (MASK) {
       const int k0 = t * KV;
 #pragma unroll
@@ -525,10 +552,11 @@ k_attn(const AttnArgs a) {
       l_run[qs] += ps;
     }
     } else {                                          // fp16: classic running-max form (fp16 P needs p <= 1)
+    const float cc = BIAS ? 1.f : a.c;             // (the biased scores are already in log2 units)
     const float m_new = fmaxf(m_run[qs], mx);
-    const float mc = m_new * a.c;
+    const float mc = m_new * cc;
     if (__builtin_amdgcn_ballot_w64(m_new != m_run[qs]) != 0) {              // wave-uniform: rescale only when needed
-      const float alpha = __builtin_amdgcn_exp2f((m_run[qs] - m_new) * a.c);
+      const float alpha = __builtin_amdgcn_exp2f((m_run[qs] - m_new) * cc);
       if (!ONES) l_run[qs] *= alpha;
 #pragma unroll
       for (int d = 0; d < NDB; ++d)
@@ -539,7 +567,7 @@ k_attn(const AttnArgs a) {
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-      for (int i = 0; i < 16; ++i) st[qs][kb][i] = __builtin_amdgcn_exp2f(fmaf(st[qs][kb][i], a.c, -mc));
+      for (int i = 0; i < 16; ++i) st[qs][kb][i] = __builtin_amdgcn_exp2f(fmaf(st[qs][kb][i], cc, -mc));
     if (!ONES) {
       float ps = 0.f;
 #pragma unroll
@@ -978,6 +1006,15 @@ static int g_attn_nomax = 1;         // debug A/B switch (sdn_debug_set_attn_nom
 
 template <typename T, int HD>
 int launch(const AttnArgs& a, int batch, int heads, hipStream_t st) {
+  if (a.bias) {
+    if constexpr (HD == 64) {
+      if (a.q2 || a.causal) return SDN_E_INVALID;
+      hipLaunchKernelGGL((k_attn<T, HD, false, true, true, 1, true>), dim3(a.nqb * a.npairs), dim3(THREADS), 0, st, a);
+      return sdn_launch_status();
+    } else {
+      return SDN_E_INVALID;                     // biased attention is instantiated for d = 64 (T5) only
+    }
+  }
   if (a.causal || a.kmask) {
     if constexpr (HD == 64) {
       if (a.q2) return SDN_E_INVALID;
@@ -1017,7 +1054,7 @@ static int g_attn_head_inner = 1;    // debug A/B switch (sdn_debug_set_attn_hea
 template <typename T>
 int run(const void* q, const void* k, const void* v, void* out, int32_t batch, int32_t heads, int32_t nq, int32_t nk,
         int32_t head_dim, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo, float scale, void* stream,
-        const sdn_attn_segment2* s2 = nullptr, int causal = 0, const int* kmask = nullptr) {
+        const sdn_attn_segment2* s2 = nullptr, int causal = 0, const int* kmask = nullptr, const float* bias = nullptr) {
   if (!q || !k || !v || !out || batch < 0 || heads <= 0 || nq <= 0 || nk <= 0) return SDN_E_INVALID;
   if ((ldq & 7) || (ldk & 7) || (ldv & 7) || (ldo & 3) || nk > 65535) return SDN_E_INVALID;
   if (ldq < heads * head_dim || ldk < heads * head_dim || ldv < heads * head_dim || ldo < heads * head_dim)
@@ -1027,7 +1064,7 @@ int run(const void* q, const void* k, const void* v, void* out, int32_t batch, i
   if (batch == 0) return SDN_OK;
   AttnArgs a{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v, (unsigned short*)out,
              nq, nk, ldq, ldk, ldv, ldo, scale * 1.4426950408889634f, heads, (nq + QB - 1) / QB, batch * heads,
-             nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0, causal, kmask, g_attn_nomax};
+             nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0, causal, kmask, g_attn_nomax, bias};
   if (!s2 && nk <= 2 * KV && (batch & 7) == 0 && g_attn_head_inner) a.head_inner = 1;
   if (causal && nq != nk) return SDN_E_INVALID;
   if (s2) {                                                  // joint attention over two token streams (nq == nk)
@@ -1089,6 +1126,18 @@ extern "C" int sdn_masked_attention(int32_t dtype, const void* q, const void* k,
                                         causal ? 1 : 0, key_mask);
   return sdn_attn_detail::run<SdnBF16>(q, k, v, out, batch, heads, n, n, head_dim, ldq, ldk, ldv, ldo, scale, stream, nullptr,
                                        causal ? 1 : 0, key_mask);
+}
+
+// T5 self-attention: softmax(scale Q K^T + bias[head, key - query] + key mask) V, bidirectional (sdn.h)
+extern "C" int sdn_bias_attention(int32_t dtype, const void* q, const void* k, const void* v, void* out, const float* bias,
+                                  const int32_t* key_mask, int32_t batch, int32_t heads, int32_t n, int32_t head_dim, int32_t ldq,
+                                  int32_t ldk, int32_t ldv, int32_t ldo, float scale, void* stream) {
+  if (!bias || (reinterpret_cast<uintptr_t>(bias) & 3) || n < 2 || n > 512 || head_dim != 64 || dtype < 0 || dtype > 1) return SDN_E_INVALID;
+  if (dtype == 1)
+    return sdn_attn_detail::run<SdnF16>(q, k, v, out, batch, heads, n, n, head_dim, ldq, ldk, ldv, ldo, scale, stream, nullptr, 0,
+                                        key_mask, bias);
+  return sdn_attn_detail::run<SdnBF16>(q, k, v, out, batch, heads, n, n, head_dim, ldq, ldk, ldv, ldo, scale, stream, nullptr, 0,
+                                       key_mask, bias);
 }
 
 extern "C" void sdn_debug_set_attn_head_inner(int on) { sdn_attn_detail::g_attn_head_inner = on; }

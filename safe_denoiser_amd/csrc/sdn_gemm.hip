@@ -561,6 +561,7 @@ k_splitk_reduce(const float* __restrict__ part, int splits, long slice, int M, i
 // Slices worth cutting the k loop into (1 = do not split): only when the tile grid leaves most CUs idle and the k loop
 // is long enough for a slice to amortise its prologue; the plan builder sizes the partial buffer from this.
 int sdn_gemm_pick_split(int M, int N, int K, int act, int out_kind) {
+  if (act == SDN_ACT_GEGLU_TANH) act = SDN_ACT_GEGLU;
   if (out_kind != SDN_OUT_BF16 || act == SDN_ACT_GEGLU || (N & 3)) return 1;
   const int nrep = sdn_gemm_pick_tile(M, N, K, act, 0);
   const int bm = nrep >= 8 ? 256 : 128;
@@ -634,6 +635,7 @@ using namespace sdn_gemm_detail;
 
 // Picks the widest N tile that divides N (160 for SD-v1.4 widths, 128 for GEGLU / MMDiT widths, 64, 32).
 int sdn_gemm_pick_nrep(int n_padded, int act) {
+  if (act == SDN_ACT_GEGLU_TANH) act = SDN_ACT_GEGLU;         // same tiles: only the gate's nonlinearity differs
   if (act == SDN_ACT_GEGLU) return (n_padded % 128 == 0) ? 4 : ((n_padded % 64 == 0) ? 2 : 0);
   if (n_padded % 160 == 0) return 5;
   if (n_padded % 128 == 0) return 4;
@@ -668,6 +670,7 @@ extern "C" void sdn_debug_gemm_last_launch(int* out, int n) {
 // Tile choice with the grid in mind: when the widest tile leaves the 256 CUs (x2 resident blocks) underfilled
 // (the 8x8 / 16x16 levels at small batch), fall back to BN = 64 to multiply the number of workgroups.
 int sdn_gemm_pick_tile(int M, int N, int K, int act, int epilogue_reads) {
+  if (act == SDN_ACT_GEGLU_TANH) act = SDN_ACT_GEGLU;
   int nrep = sdn_gemm_pick_nrep(N, act);
   if (g_gemm_variant == 2) return nrep;                      // debug: heuristics off
   // big tile (256 rows, 8 waves, 1 block/CU) when it still fills the chip: >= ~3/4 of the 256 CUs get a tile
@@ -704,14 +707,32 @@ static int sdn_gemm_impl(int dtype, const sdn_gemm_desc* d, const void* a, const
                          void* stream, void* partials = nullptr, size_t partial_bytes = 0, const float* ln_c = nullptr,
                          const float* ln_d = nullptr, float ln_eps = 0.f, const float* ln_stats = nullptr, float* col_stats = nullptr) {
   if (!d || !a || !w || !out) return SDN_E_INVALID;
+  // Two forms that reuse existing kernel paths under their own descriptor codes:
+  //   act SDN_ACT_GEGLU_TANH = the GEGLU tile with tanh-GELU on the gate (plain 16-bit GEMM only);
+  //   f32_stream = F32 residual + F32 output straight from the accumulators over ORDINARY 16-bit operands of either dtype: a
+  //   transformer's f32 residual stream fed by 16-bit projections (T5).  The kernel's residual prologue and store path are the
+  //   ones x3_out = 1 uses (GemmArgs.x3_out), which never look at the operand type.
+  sdn_gemm_desc dd = *d;
+  const bool glu_tanh = dd.act == SDN_ACT_GEGLU_TANH;
+  const bool stream32 = dd.f32_stream != 0;
+  if (glu_tanh) {
+    if (dd.x3_out || stream32 || ln_c || ln_d || partials || dd.split_k > 1 || col_stats) return SDN_E_INVALID;
+    dd.act = SDN_ACT_GEGLU;
+  }
+  if (stream32) {
+    if (dd.f32_stream != 1 || dd.x3_out || dd.act != SDN_ACT_NONE || dd.a_mode != SDN_A_PLAIN || dd.res_pre || dd.residual_bcast ||
+        dd.out_kind != SDN_OUT_F32 || rowgate || dd.split_k > 1 || partials || ln_c || ln_d || col_stats || (dd.n_valid > 0 && dd.n_valid != dd.N))
+      return SDN_E_INVALID;
+  }
+  d = &dd;
   if (d->M < 0 || d->N <= 0 || d->K <= 0 || (d->K % BK) != 0) return SDN_E_INVALID;
   if (d->M == 0) return SDN_OK;
   const int n_valid = d->n_valid > 0 ? d->n_valid : d->N;
   if (n_valid > d->N) return SDN_E_INVALID;
   if (sdn_gemm_pick_nrep(d->N, d->act) == 0) return SDN_E_INVALID;
-  const int x3 = d->x3_out;
+  const int x3 = stream32 ? 1 : d->x3_out;                  // (the stream form rides the kernel's x3_out = 1 path; its checks are above)
   const bool h8 = x3 == 5;                                  // experimental: fp16 + e4m3 corrections by operand expansion
-  if (x3 < 0 || x3 > 5 || (x3 && ((dtype != 0) != h8 || rowgate || d->split_k > 1 || partials || ln_c || col_stats || n_valid != d->N)))
+  if (x3 < 0 || x3 > 5 || (x3 && !stream32 && ((dtype != 0) != h8 || rowgate || d->split_k > 1 || partials || ln_c || col_stats || n_valid != d->N)))
     return SDN_E_INVALID;
   if (h8 && (d->a_mode != SDN_A_PLAIN || d->act != SDN_ACT_NONE || (d->K % 256) != 0 || d->res_pre || (d->K1 > 0 && d->K1 < d->K)))
     return SDN_E_INVALID;
@@ -759,6 +780,7 @@ static int sdn_gemm_impl(int dtype, const sdn_gemm_desc* d, const void* a, const
   if ((rowbias || rowgate || d->residual_bcast || d->out_kind == SDN_OUT_F32_NCHW) && d->rows_per_batch <= 0) return SDN_E_INVALID;
   if (rowgate && !al16(rowgate)) return SDN_E_INVALID;
   g.x3_out = h8 ? 1 : x3;                                    // (h8: f32 rows straight from the accumulators, as x3_out = 1)
+  g.glu_tanh = glu_tanh ? 1 : 0;
   g.h8_t16 = h8 ? d->K / 128 : 0;                            // d->K counts 16-bit units of the 4-byte-per-element row: half of it is fp16
   g.act = d->act; g.out_kind = x3 ? SDN_OUT_F32 : d->out_kind; g.rows_per_batch = d->rows_per_batch; g.ld_rowbias = d->ld_rowbias;
   g.ld_rowgate = d->ld_rowgate; g.residual_bcast = d->residual_bcast;

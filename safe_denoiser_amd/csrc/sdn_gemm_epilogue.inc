@@ -143,6 +143,20 @@
         *reinterpret_cast<uint2*>(smem + ml * CW_PAD + nl * 2) = pk;
       }
     }
+  } else if (g.act == 2 && g.glu_tanh) {                      // gated tanh-GELU (T5 gelu_new): same column pairs, same half-width tile
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int ml = (wm % WM_PER_PASS) * 64 + i * 16 + fr;
+#pragma unroll
+      for (int j = 0; j + 1 < NREP; j += 2) {
+        const f32x4 hv = acc[i][j], gv = acc[i][j + 1];
+        uint2 pk;
+        pk.x = T::pack2(hv[0] * gelu_tanh(gv[0]), hv[1] * gelu_tanh(gv[1]));
+        pk.y = T::pack2(hv[2] * gelu_tanh(gv[2]), hv[3] * gelu_tanh(gv[3]));
+        const int nl = ((wn * 16 * NREP + j * 16) >> 1) + fq * 4;
+        *reinterpret_cast<uint2*>(smem + ml * CW_PAD + nl * 2) = pk;
+      }
+    }
   } else if (g.act == 2) {                                    // GEGLU: value / gate column pairs -> half-width tile
 #pragma unroll
     for (int i = 0; i < 4; ++i) {

@@ -39,7 +39,8 @@ enum Space { SP_NONE = 0, SP_W = 1, SP_WS = 2, SP_LATENTS = 3, SP_TEXT = 4, SP_O
 struct Ref { int space = SP_NONE; int64_t off = 0; };
 
 enum OpKind { OP_TEMB, OP_CONV_IN, OP_GEMM, OP_GN, OP_LN, OP_ATTN, OP_PATCHIFY, OP_UNPATCHIFY, OP_LATENT_MIX, OP_SOFTMAX,
-              OP_TRANSPOSE, OP_GAUSS, OP_REPEAT, OP_CLIP_EMBED, OP_MATTN, OP_ROWSTATS, OP_FFN, OP_SPLIT3 };
+              OP_TRANSPOSE, OP_GAUSS, OP_REPEAT, OP_CLIP_EMBED, OP_MATTN, OP_ROWSTATS, OP_FFN, OP_SPLIT3,
+              OP_RMSNORM, OP_EMBED, OP_T5_BIAS, OP_BATTN };
 
 struct Op {
   int kind;
@@ -135,11 +136,13 @@ struct sdn_unet {
   bool is_vae_encoder = false;
   bool is_clip = false;
   sdn_clip_config ccfg;
-  const void* clip_mask = nullptr;      // key-padding mask of the forward in flight (nullable)
+  const void* clip_mask = nullptr;      // key-padding mask of the forward in flight (nullable; CLIP and T5)
+  bool is_t5 = false;
+  sdn_t5_config tcfg;
   std::vector<sdn_param_info> params;
   std::map<std::string, int> param_index;
   int64_t weight_bytes = 0;
-  std::map<int, Plan> plans;
+  std::map<int, Plan> plans;            // by batch (T5: by batch * 1024 + n)
   int tproj_total = 0;
   int64_t subbatch_bytes = 0;            // >0: run transformer blocks on batch slices of at most this many bytes per
                                          // activation.  Measured at B = 64 (tools/profile_ops.py, SUBBATCH=...): 48 MB
@@ -184,6 +187,7 @@ struct sdn_unet {
   }
   std::vector<hipEvent_t> ev;          // 2 per op of the profiled forward
   int profiled_batch = 0;
+  int profiled_n = 0;                  // T5: sequence length of the profiled forward
 };
 
 namespace {
@@ -193,6 +197,7 @@ struct Builder {
   Plan* plan;
   Arena arena;
   int B;
+  int seq = 0;               // T5 plans: the sequence length this plan is built for
   int es = 2;                // bytes per activation / matrix-weight element: 2 (bf16 | f16 storage) or 4 (the fp32 precision mode)
   bool x3t = false;          // bf16x3 by operand expansion (SD-v1.4 UNet plan, dtype 3): GEMM operands are bf16 hi|lo|hi triples
   bool x3t_hold = false;     // ... except inside this scope (the per-sample time-embedding GEMMs: M = batch, nothing to gain)
@@ -1327,18 +1332,112 @@ struct Builder {
     drop(x);
     plan->ws_bytes = arena.peak;
   }
+  // =================================================================================================
+  // T5 encoder (SD-v3 text_encoder_3): `self.text_encoder_3(input_ids, attention_mask)[0]` (models/sdv3/safe_denoiser_pipeline.py
+  // :316-334, :731-768, :797-827).  transformers' T5EncoderModel (third party): token embedding (no position table), pre-RMS-norm
+  // layers of bidirectional self-attention with a shared relative-position bias and NO 1/sqrt(d) scale, gated tanh-GELU
+  // feed-forward, final RMS norm; no biases.  The residual stream x stays F32: both output projections add into it in place.
+  // =================================================================================================
+  // one SDN_ACT_GEGLU* weight from two state_dict tensors: value / gate row blocks of 16 interleaved in ONE [2F, K] region
+  Ref glu_pair(const std::string& value_name, const std::string& gate_name, int F, int K) {
+    auto it = u->param_index.find(value_name);
+    if (it != u->param_index.end()) return Ref{SP_W, u->params[it->second].offset};
+    const int64_t base = u->weight_bytes;
+    const std::string* names[2] = {&value_name, &gate_name};
+    for (int i = 0; i < 2; ++i) {
+      sdn_param_info pi; memset(&pi, 0, sizeof(pi));
+      snprintf(pi.name, sizeof(pi.name), "%s", names[i]->c_str());
+      pi.kind = i == 0 ? SDN_P_GLU_VALUE : SDN_P_GLU_GATE; pi.rows = F; pi.cols = K; pi.rows_padded = F;
+      pi.offset = base + (int64_t)i * 16 * K * es;
+      u->param_index[*names[i]] = (int)u->params.size();
+      u->params.push_back(pi);
+    }
+    u->weight_bytes += ((int64_t)2 * F * K * es + 255) & ~(int64_t)255;
+    return Ref{SP_W, base};
+  }
+  void t5_gemm(int64_t M, int N, int K, Ref a, Ref w, Ref out, int act_, bool into_stream) {
+    Op o; o.kind = OP_GEMM; memset(&o.gd, 0, sizeof(o.gd));
+    o.gd.M = (int)M; o.gd.N = N; o.gd.K = K; o.gd.a_mode = SDN_A_PLAIN; o.gd.act = act_; o.gd.out_kind = SDN_OUT_BF16;
+    o.a = a; o.w = w; o.out = out;
+    if (into_stream) { o.gd.f32_stream = 1; o.gd.out_kind = SDN_OUT_F32; o.residual = out; }   // x += A W^T: F32 residual and output, the same tensor
+    o.flops = 2.0 * (double)M * (double)N * (double)K;
+    o.bytes = 2.0 * ((double)M * K + (double)N * K) + (into_stream ? 8.0 : (act_ == SDN_ACT_GEGLU_TANH ? 1.0 : 2.0)) * (double)M * N;
+    snprintf(o.label, sizeof(o.label), "k_gemm<%d>%s", sdn_gemm_pick_tile((int)M, N, K, act_), into_stream ? "/f32" : "");
+    push_gemm(o);
+  }
+  void t5_rmsnorm(Ref x, bool x_f32, int64_t rows, int C, Ref w, Ref out) {
+    Op o; o.kind = OP_RMSNORM; o.a = x; o.mod = x_f32 ? 1 : 0; o.rows = rows; o.c1 = C; o.eps = u->tcfg.eps; o.w = w; o.out = out;
+    o.bytes = (x_f32 ? 6.0 : 4.0) * (double)rows * C; snprintf(o.label, sizeof(o.label), "k_rmsnorm"); plan->ops.push_back(o);
+  }
+  void build_t5() {
+    const sdn_t5_config& c = u->tcfg;
+    const int D = c.d_model, F = c.d_ff, H = c.num_heads, I = H * c.d_kv, n = seq;
+    const int64_t rows = (int64_t)B * n;
+    Ref tok = param("embed_tokens.weight", SDN_P_MAT, c.vocab_size, D);
+    Act x = act(rows, D, n, 0, 4);
+    { Op o; o.kind = OP_EMBED; o.a = Ref{SP_LATENTS, 0}; o.w = tok; o.out = R(x); o.rows = rows; o.c1 = D; o.c2 = c.vocab_size;
+      o.bytes = 6.0 * rows * D; snprintf(o.label, sizeof(o.label), "k_embed_tokens"); plan->ops.push_back(o); }
+    Act bias = act(H, 2 * n - 1, 0, 0, 4);               // computed once per forward, shared by every layer
+    char buf[96];
+    for (int l = 0; l < c.num_layers; ++l) {
+      snprintf(buf, sizeof(buf), "block.%d.layer", l);
+      const std::string p = buf;
+      Ref n1 = param(p + ".0.layer_norm.weight", SDN_P_VEC_F32, D, 0);
+      Ref qkvw = stacked({p + ".0.SelfAttention.q.weight", p + ".0.SelfAttention.k.weight", p + ".0.SelfAttention.v.weight"}, I, D);
+      Ref ow = param(p + ".0.SelfAttention.o.weight", SDN_P_MAT, D, I);
+      if (l == 0) {
+        Ref tab = param(p + ".0.SelfAttention.relative_attention_bias.weight", SDN_P_MAT, c.num_buckets, H);
+        Op o; o.kind = OP_T5_BIAS; o.w = tab; o.out = R(bias); o.heads = H; o.nq = n; o.bytes = 4.0 * H * (2 * n - 1);
+        snprintf(o.label, sizeof(o.label), "k_t5_bias"); plan->ops.push_back(o);
+      }
+      Ref n2 = param(p + ".1.layer_norm.weight", SDN_P_VEC_F32, D, 0);
+      Ref wi = glu_pair(p + ".1.DenseReluDense.wi_1.weight", p + ".1.DenseReluDense.wi_0.weight", F, D);
+      Ref wo = param(p + ".1.DenseReluDense.wo.weight", SDN_P_MAT, D, F);
+      Act ln = act(rows, D, n, 0);
+      t5_rmsnorm(R(x), true, rows, D, n1, R(ln));
+      Act qkv = act(rows, 3 * I, n, 0);
+      t5_gemm(rows, 3 * I, D, R(ln), qkvw, R(qkv), SDN_ACT_NONE, false);
+      Act at = act(rows, I, n, 0);
+      { Op o; o.kind = OP_BATTN; o.a = R(qkv); o.k = Ref{SP_WS, qkv.off + (int64_t)I * es}; o.v = Ref{SP_WS, qkv.off + (int64_t)2 * I * es};
+        o.aux = R(bias); o.out = R(at); o.batch = B; o.heads = H; o.nq = n; o.nk = n; o.hd = c.d_kv; o.ldq = o.ldk = o.ldv = 3 * I; o.ldo = I;
+        o.scale = 1.0f;                                  // T5 folds the scale into its initialisation
+        o.flops = 4.0 * B * H * (double)n * n * o.hd; o.bytes = 2.0 * 4.0 * rows * I;
+        snprintf(o.label, sizeof(o.label), "k_attn<%d>/bias", o.hd); plan->ops.push_back(o); plan->flops += o.flops; plan->attn_flops += o.flops; }
+      drop(qkv);
+      t5_gemm(rows, D, I, R(at), ow, R(x), SDN_ACT_NONE, true);
+      drop(at);
+      t5_rmsnorm(R(x), true, rows, D, n2, R(ln));
+      Act h = act(rows, F, n, 0);
+      t5_gemm(rows, 2 * F, D, R(ln), wi, R(h), SDN_ACT_GEGLU_TANH, false);
+      drop(ln);
+      t5_gemm(rows, D, F, R(h), wo, R(x), SDN_ACT_NONE, true);
+      drop(h);
+    }
+    Ref fn = param("final_layer_norm.weight", SDN_P_VEC_F32, D, 0);
+    t5_rmsnorm(R(x), true, rows, D, fn, Ref{SP_OUT, 0});
+    drop(x); drop(bias);
+    plan->ws_bytes = arena.peak;
+  }
 };
 
-Plan* get_plan(sdn_unet* u, int batch) {
-  auto it = u->plans.find(batch);
+// n: the sequence length of a T5 plan (ignored by every other plan); 0 = the longest one (512), which bounds the workspace of any n
+Plan* get_plan(sdn_unet* u, int batch, int n = 0) {
+  if (u->is_t5 && n == 0) n = 512;
+  const int key = u->is_t5 ? batch * 1024 + n : batch;
+  auto it = u->plans.find(key);
   if (it != u->plans.end()) return &it->second;
-  Plan& p = u->plans[batch];
+  if (u->is_t5 && u->plans.size() >= 64) {                      // ragged lengths: bounded cache (no forward is in flight on the host side)
+    u->plans.clear();
+    u->profiled_batch = 0;                                      // ... and a profiled forward's plan is gone with it: nothing left to read
+  }
+  Plan& p = u->plans[key];
   p.batch = batch;
   Builder b{u, &p};
   b.B = batch;
+  b.seq = n;
   b.es = (!u->is_vae && (u->is_mmdit ? u->mcfg.dtype : u->cfg.dtype) >= 2) ? 4 : 2;   // fp32 storage: SD-v1.4 UNet, CLIP and MMDiT plans
   b.x3t = !u->is_vae && !u->is_mmdit && !u->is_clip && u->cfg.dtype == 3 && u->x3_expand;
-  if (u->is_clip) b.build_clip(); else if (u->is_vae_encoder) b.build_vae_encoder(); else if (u->is_vae) b.build_vae(); else if (u->is_mmdit) b.build_mmdit(); else b.build();
+  if (u->is_t5) b.build_t5(); else if (u->is_clip) b.build_clip(); else if (u->is_vae_encoder) b.build_vae_encoder(); else if (u->is_vae) b.build_vae(); else if (u->is_mmdit) b.build_mmdit(); else b.build();
   return &p;
 }
 
@@ -1463,6 +1562,22 @@ int sdn_clip_create(const sdn_clip_config* cfg, sdn_unet** out) {
 int sdn_clip_forward(sdn_unet* m, const void* weights, const int32_t* input_ids, const int32_t* attention_mask,
                      void* last_hidden_state, int32_t batch, void* workspace, size_t workspace_bytes, void* stream);
 
+int sdn_t5_create(const sdn_t5_config* cfg, sdn_unet** out) {
+  if (!cfg || !out) return SDN_E_INVALID;
+  if (cfg->vocab_size <= 0 || cfg->d_model <= 0 || cfg->d_model % 64 != 0 || cfg->d_kv != 64 || cfg->d_ff <= 0 || cfg->d_ff % 64 != 0 ||
+      cfg->num_layers <= 0 || cfg->num_heads <= 0 || cfg->num_heads > 512 || cfg->num_buckets < 4 || cfg->num_buckets > 64 ||
+      (cfg->num_buckets & 3) || cfg->max_distance <= cfg->num_buckets / 4 || !(cfg->eps > 0.f) || cfg->dtype < 0 || cfg->dtype > 1)
+    return SDN_E_INVALID;                                       // (dtype 2 / 3, the fp32-storage modes, are not built yet)
+  sdn_unet* u = new sdn_unet();
+  memset(&u->cfg, 0, sizeof(u->cfg));
+  u->cfg.dtype = cfg->dtype;
+  u->tcfg = *cfg;
+  u->is_t5 = true;
+  get_plan(u, 1);                                               // registers the parameter manifest (independent of batch and n)
+  *out = u;
+  return SDN_OK;
+}
+
 int sdn_unet_prepare(sdn_unet* u, void* weights, void* stream) {
   if (!u || !weights) return SDN_E_INVALID;
   char* W = (char*)weights;
@@ -1502,6 +1617,7 @@ size_t sdn_unet_weight_bytes(const sdn_unet* u) { return u ? (size_t)u->weight_b
 static int vae_chunk(const sdn_unet* v);
 size_t sdn_unet_workspace_bytes(sdn_unet* u, int32_t batch) {
   if (!u || batch <= 0) return 0;
+  if (u->is_t5) return sdn_t5_workspace_bytes(u, batch, 512);      // the sequence length is a call-time argument: the bound for any n
   if (u->is_vae) {                                                 // VAE entry points run large batches in chunks of vae_chunk()
     const int cap = vae_chunk(u);
     if (cap == 0) return 0;
@@ -1519,7 +1635,7 @@ double sdn_unet_flops(sdn_unet* u, int32_t batch, double* attn) {
 }
 
 static int run_plan(sdn_unet* u, const void* weights, const float* latents, float timestep, const void* text,
-                    const void* pooled, float* out, int32_t batch, void* workspace, size_t workspace_bytes, void* stream);
+                    const void* pooled, float* out, int32_t batch, void* workspace, size_t workspace_bytes, void* stream, int n = 0);
 
 // Images one plan invocation of a VAE takes: byte offsets inside one activation are 32-bit in the GEMM's DMA descriptors, so the
 // largest tensor (batch x side^2 x widest channel count x 2 B) must stay below 4 GiB; larger batches are cut into chunks INSIDE
@@ -1576,16 +1692,37 @@ int sdn_clip_forward(sdn_unet* m, const void* weights, const int32_t* input_ids,
                   batch, workspace, workspace_bytes, stream);
 }
 
+size_t sdn_t5_workspace_bytes(sdn_unet* m, int32_t batch, int32_t n) {
+  if (!m || !m->is_t5 || batch <= 0 || batch > (1 << 20) || n < 2 || n > 512) return 0;
+  const int64_t b = get_plan(m, batch, n)->ws_bytes;
+  return b < 0 ? 0 : (size_t)b;
+}
+
+double sdn_t5_flops(sdn_unet* m, int32_t batch, int32_t n, double* attn) {
+  if (!m || !m->is_t5 || batch <= 0 || batch > (1 << 20) || n < 2 || n > 512) return 0.0;
+  Plan* p = get_plan(m, batch, n);
+  if (attn) *attn = p->attn_flops;
+  return p->flops;
+}
+
+int sdn_t5_forward(sdn_unet* m, const void* weights, const int32_t* input_ids, const int32_t* attention_mask, int32_t n,
+                   void* out, int32_t batch, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!m || !m->is_t5 || n < 2 || n > 512 || batch > (1 << 20)) return SDN_E_INVALID;
+  m->clip_mask = attention_mask;
+  return run_plan(m, weights, (const float*)input_ids, 0.f, weights /* no text operand */, nullptr, (float*)out, batch, workspace,
+                  workspace_bytes, stream, n);
+}
+
 int sdn_unet_forward(sdn_unet* u, const void* weights, const float* latents, float timestep, const void* text,
                      float* out, int32_t batch, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!u || u->is_mmdit || u->is_vae || u->is_clip) return SDN_E_INVALID;
+  if (!u || u->is_mmdit || u->is_vae || u->is_clip || u->is_t5) return SDN_E_INVALID;
   return run_plan(u, weights, latents, timestep, text, nullptr, out, batch, workspace, workspace_bytes, stream);
 }
 
 int sdn_mmdit_forward(sdn_unet* u, const void* weights, const float* latents, float timestep, const void* text,
                       const void* pooled, float* out, int32_t batch, void* workspace, size_t workspace_bytes,
                       void* stream) {
-  if (!u || !u->is_mmdit || u->is_vae || u->is_clip || !pooled) return SDN_E_INVALID;
+  if (!u || !u->is_mmdit || u->is_vae || u->is_clip || u->is_t5 || !pooled) return SDN_E_INVALID;
   return run_plan(u, weights, latents, timestep, text, pooled, out, batch, workspace, workspace_bytes, stream);
 }
 
@@ -1787,6 +1924,19 @@ static int launch_ops(sdn_unet* u, Plan* p, const char* W, const char* WS, const
         rc = sdn_masked_attention(f16 ? 1 : 0, P(o.a), P(o.k), P(o.v), (void*)P(o.out), (const int32_t*)u->clip_mask, 1, o.batch,
                                   o.heads, o.nq, o.hd, o.ldq, o.ldk, o.ldv, o.ldo, o.scale, stream);
         break;
+      case OP_RMSNORM:
+        rc = sdn_rmsnorm(f16 ? 1 : 0, P(o.a), o.mod, o.rows, o.c1, o.eps, (const float*)P(o.w), (void*)P(o.out), stream);
+        break;
+      case OP_EMBED:
+        rc = sdn_embed_tokens(f16 ? 1 : 0, (const int32_t*)P(o.a), P(o.w), o.rows, o.c1, o.c2, (float*)P(o.out), stream);
+        break;
+      case OP_T5_BIAS:
+        rc = sdn_t5_relative_bias(f16 ? 1 : 0, P(o.w), u->tcfg.num_buckets, u->tcfg.max_distance, o.heads, o.nq, (float*)P(o.out), stream);
+        break;
+      case OP_BATTN:
+        rc = sdn_bias_attention(f16 ? 1 : 0, P(o.a), P(o.k), P(o.v), (void*)P(o.out), (const float*)P(o.aux), (const int32_t*)u->clip_mask,
+                                o.batch, o.heads, o.nq, o.hd, o.ldq, o.ldk, o.ldv, o.ldo, o.scale, stream);
+        break;
       case OP_REPEAT:
         rc = sdn_repeat(P(o.a), (size_t)o.rows, o.c1, (void*)P(o.out), stream);
         break;
@@ -1838,9 +1988,9 @@ static int launch_ops(sdn_unet* u, Plan* p, const char* W, const char* WS, const
 
 
 static int run_plan(sdn_unet* u, const void* weights, const float* latents, float timestep, const void* text,
-                    const void* pooled, float* out, int32_t batch, void* workspace, size_t workspace_bytes, void* stream) {
+                    const void* pooled, float* out, int32_t batch, void* workspace, size_t workspace_bytes, void* stream, int n) {
   if (!u || !weights || !latents || !text || !out || !workspace || batch <= 0) return SDN_E_INVALID;
-  Plan* p = get_plan(u, batch);
+  Plan* p = get_plan(u, batch, n);
   if (p->ws_bytes < 0) return SDN_E_INVALID;                      // e.g. batch not a multiple of latent_repeat
   if (workspace_bytes < (size_t)p->ws_bytes) return SDN_E_WORKSPACE;
   const char* W = (const char*)weights; const char* WS = (const char*)workspace;
@@ -1850,10 +2000,10 @@ static int run_plan(sdn_unet* u, const void* weights, const float* latents, floa
   if (prof) {                                    // opt-in diagnostics: HIP events around every launch of this forward
     u->profile_next = false;
     while (u->ev.size() < 2 * p->ops.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return SDN_E_LAUNCH; u->ev.push_back(e); }
-    u->profiled_batch = batch;
+    u->profiled_batch = batch; u->profiled_n = n;
   }
   hipStream_t hs = (hipStream_t)stream;
-  if (u->use_graph && !prof && !u->is_vae && !u->is_clip && p->tscalar_off >= 0) {
+  if (u->use_graph && !prof && !u->is_vae && !u->is_clip && !u->is_t5 && p->tscalar_off >= 0) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(hs, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
       // Graph mode: small batches are launch-bound (~850 launches per forward); the forward is captured once per
@@ -1914,7 +2064,7 @@ static void drop_graphs(sdn_unet* u) {
 }
 
 void sdn_unet_set_split_k(sdn_unet* u, int32_t on) {
-  if (!u || u->split_k == (on != 0)) return;
+  if (!u || u->is_t5 || u->split_k == (on != 0)) return;        // (the T5 plan's GEMMs add into an f32 stream: no split-K form)
   if (!u->is_vae && (u->is_mmdit ? u->mcfg.dtype : u->cfg.dtype) >= 2) return;   // fp32-storage modes have no split-K form
   u->split_k = on != 0;
   drop_graphs(u);
@@ -2004,7 +2154,7 @@ extern "C" void sdn_debug_set_subbatch_bytes(sdn_unet* u, long long bytes) {
 // out[i*6 + {0..5}] = {ms, flops, bytes, M, N, K}; labels[i*24..] = kernel label.  Returns the op count.
 extern "C" int sdn_debug_profile_ops(sdn_unet* u, double* out, char* labels, int max_ops) {
   if (!u || !out || !labels || u->profiled_batch <= 0) return -1;
-  Plan* p = get_plan(u, u->profiled_batch);
+  Plan* p = get_plan(u, u->profiled_batch, u->profiled_n);
   int n = 0;
   for (size_t i = 0; i < p->ops.size() && n < max_ops; ++i, ++n) {
     if (hipEventSynchronize(u->ev[2 * i + 1]) != hipSuccess) return -2;
@@ -2022,7 +2172,7 @@ extern "C" int sdn_debug_profile_ops(sdn_unet* u, double* out, char* labels, int
 
 int sdn_unet_profile_read(sdn_unet* u, sdn_profile_row* rows, int32_t max_rows) {
   if (!u || !rows || max_rows <= 0 || u->profiled_batch <= 0) return SDN_E_INVALID;
-  Plan* p = get_plan(u, u->profiled_batch);
+  Plan* p = get_plan(u, u->profiled_batch, u->profiled_n);
   if (u->ev.size() < 2 * p->ops.size()) return SDN_E_INVALID;
   int n = 0;
   for (size_t i = 0; i < p->ops.size(); ++i) {
