@@ -186,6 +186,10 @@ int sdn_flow_renoise(const float* x0r, const float* x1, const float* z, int64_t 
 #define SDN_ACT_QUICK_GELU 4 /* x * sigmoid(1.702 x) -- CLIP text encoder MLP                     */
 #define SDN_ACT_GEGLU_TANH 5 /* the layout of SDN_ACT_GEGLU with out = v * gelu_tanh(g): T5 gated-gelu (gelu_new(wi_0 x) * wi_1 x,
                                value rows = wi_1, gate rows = wi_0); plain sdn_gemm_bf16 / sdn_gemm_f16 only             */
+#define SDN_ACT_GELU      7   /* x * Phi(x), the exact (erf) GELU, not gated -- OpenCLIP bigG's MLP (hidden_act = "gelu").  16-bit GEMMs: a
+                               staged 16-bit output with no residual / row gate / split-K only (their epilogue evaluates the
+                               erf form the SDN_ACT_GEGLU gate uses, |error| <= 2.6e-5); sdn_gemm_f32 / sdn_gemm_x3: erff, any
+                               output.  Code 6 is not assigned: every GEMM entry point rejects it                          */
 #define SDN_OUT_BF16      0   /* [M, ldc] bf16                                                */
 #define SDN_OUT_F32       1   /* [M, ldc] f32                                                 */
 #define SDN_OUT_F32_NCHW  2   /* [B, n_valid, rows_per_batch] f32 (conv_out -> latent layout) */
@@ -647,6 +651,51 @@ int sdn_clip_embed_f32(const int32_t* input_ids, const void* token_embedding, co
 int sdn_masked_attention_f32(const void* q, const void* k, const void* v, void* out, const int32_t* key_mask, int32_t causal,
                              int32_t batch, int32_t heads, int32_t n, int32_t head_dim, int32_t ldq, int32_t ldk, int32_t ldv,
                              int32_t ldo, float scale, void* stream);
+
+/* ---- CLIP text encoder WITH projection (SD-v3 text_encoder = CLIP-L, text_encoder_2 = OpenCLIP bigG) ---------------------------
+ * Replaces `text_encoder(input_ids, output_hidden_states=True)` (transformers CLIPTextModelWithProjection, third party) as
+ * models/sdv3/safe_denoiser_pipeline.py:379-386 reads it: `prompt_embeds[0]` = text_embeds = text_projection(final_layer_norm(
+ * last)[pooling position]) and `hidden_states[-(clip_skip + 2)]`, the un-normed output of an inner layer.  The plan is the CLIP
+ * plan above with the MLP activation a config field, a tap after layer L - hidden_tap, and -- instead of final_layer_norm over all
+ * 77 rows -- the pooled row of each sequence gathered and normed (sdn_clip_eos_rows) and projected by an ordinary plan GEMM.
+ * Handle = sdn_unet; manifest keys are sdn_clip_config's plus `text_projection.weight` ([projection_dim, hidden], no bias). */
+typedef struct sdn_clip_proj_config {
+  int32_t vocab_size;                    /* 49408                                                      */
+  int32_t hidden_size, intermediate_size;/* 768, 3072 (CLIP-L) | 1280, 5120 (bigG); hidden % 128 == 0, <= 1280 */
+  int32_t num_layers, num_heads;         /* 12, 12 | 32, 20 (head dim must be 64)                      */
+  int32_t max_position_embeddings;       /* 77 = the sequence length every call uses                   */
+  int32_t dtype;                         /* 0 = bf16, 1 = fp16, 2 = fp32 storage, 3 = fp32 storage with bf16x3 GEMMs (as sdn_clip_config) */
+  int32_t projection_dim;                /* 768 | 1280; % 32 == 0                                      */
+  int32_t act;                           /* SDN_ACT_QUICK_GELU (CLIP-L) or SDN_ACT_GELU (bigG)         */
+  int32_t eos_token_id;                  /* 2 = transformers' legacy rule: pool at the highest id of the sequence (both SD-v3
+                                          * configs); else pool at the first position holding this id  */
+  int32_t hidden_tap;                    /* which hidden state is returned, counted from the end: 1 = the (un-normed) output of
+                                          * the last layer, 2 = hidden_states[-2] (SD-v3), clip_skip = k -> k + 2; 1 .. num_layers */
+} sdn_clip_proj_config;
+int sdn_clip_proj_create(const sdn_clip_proj_config* cfg_host, sdn_unet** out_host);
+/* hidden [B, 77, hidden_size] = hidden_states[-hidden_tap] and text_embeds [B, projection_dim] of input_ids [B, 77] int32, in
+ * the plan's storage type (16-bit, or f32 for dtype 2 / 3).  Both outputs are STRIDED so that several encoders can write column
+ * slices of one buffer (SD-v3: [B, 333, 4096] and [B, 2048]): element (b, t, c) of `hidden` goes to hidden[b * hidden_batch_stride
+ * + t * hidden_row_stride + c], element (b, c) of `text_embeds` to text_embeds[b * embeds_row_stride + c]; strides in ELEMENTS,
+ * multiples of 8, hidden_row_stride >= hidden_size, hidden_batch_stride >= 77 * hidden_row_stride, embeds_row_stride >=
+ * projection_dim; both pointers 16-byte aligned.  Nothing outside those elements is written.  Causal attention, no key mask
+ * (the SD-v3 pipeline passes none). */
+int sdn_clip_proj_forward(sdn_unet* clip, const void* weights, const int32_t* input_ids, void* hidden, int64_t hidden_batch_stride,
+                          int64_t hidden_row_stride, void* text_embeds, int64_t embeds_row_stride, int32_t batch, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* its building blocks (dtype 0 = bf16, 1 = fp16, 2 = f32 storage):
+ * sdn_clip_eos_rows: per sequence b, p = the pooling position of input_ids[b, :] (ids clamped to [0, vocab) first, as sdn_clip_embed
+ *   clamps them; eos_token_id == 2: the FIRST position of the highest id; else the first position whose id == eos_token_id, 0 when
+ *   there is none -- transformers' argmax of a 0 / 1 vector), out[b, :] = LayerNorm_eps(x[b, p, :]; gamma, beta) with two-pass f32
+ *   statistics; positions [B] int32 (nullable) receives p.  x [B, seq_len, hidden], out [B, hidden]; hidden % 4 == 0.
+ * sdn_copy_rows_strided: dst[b * dst_batch_stride + t * dst_row_stride + c] = src[(b * rows_per_batch + t) * cols + c] for a
+ *   contiguous src [batch * rows_per_batch, cols] of elem_bytes-wide elements (2 or 4); cols * elem_bytes % 16 == 0, strides in
+ *   elements with stride * elem_bytes % 16 == 0, both pointers 16-byte aligned. */
+int sdn_clip_eos_rows(int32_t dtype, const int32_t* input_ids, const void* x, const float* gamma, const float* beta, int32_t batch,
+                      int32_t seq_len, int32_t hidden, int32_t vocab, int32_t eos_token_id, float eps, void* out,
+                      int32_t* positions, void* stream);
+int sdn_copy_rows_strided(const void* src, int32_t batch, int32_t rows_per_batch, int32_t cols, int32_t elem_bytes, void* dst,
+                          int64_t dst_batch_stride, int64_t dst_row_stride, void* stream);
 
 /* ---- T5 encoder (SD-v3 text_encoder_3: the encoder every SD-v3 SAFREE decision rests on) ---------------------------------
  * Replaces `self.text_encoder_3(input_ids, attention_mask=...)[0]` (transformers T5EncoderModel, third party), called at

@@ -68,6 +68,11 @@ class ClipConfig(C.Structure):
                                          "max_position_embeddings", "dtype")]
 
 
+class ClipProjConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("vocab_size", "hidden_size", "intermediate_size", "num_layers", "num_heads",
+                                         "max_position_embeddings", "dtype", "projection_dim", "act", "eos_token_id", "hidden_tap")]
+
+
 class T5Config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("vocab_size", "d_model", "d_kv", "d_ff", "num_layers", "num_heads", "num_buckets",
                                          "max_distance")] + [("eps", C.c_float), ("dtype", C.c_int32)]
@@ -176,6 +181,10 @@ SIGNATURES = {
     "sdn_clip_embed": (C.c_int, [_i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "sdn_masked_attention": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                        _f32, _vp]),
+    "sdn_clip_proj_create": (C.c_int, [C.POINTER(ClipProjConfig), C.POINTER(_vp)]),
+    "sdn_clip_proj_forward": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i32, _vp, _sz, _vp]),
+    "sdn_clip_eos_rows": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "sdn_copy_rows_strided": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _i64, _vp]),
     "sdn_t5_create": (C.c_int, [C.POINTER(T5Config), C.POINTER(_vp)]),
     "sdn_t5_workspace_bytes": (_sz, [_vp, _i32, _i32]),
     "sdn_t5_flops": (C.c_double, [_vp, _i32, _i32, C.POINTER(C.c_double)]),

@@ -124,6 +124,28 @@ def clip_kwargs(cfg: dict) -> dict:
     return {k: cfg[k] for k in keys if k in cfg}
 
 
+def clip_projection_kwargs(cfg: dict) -> dict:
+    """CLIPTextModelWithProjection(**kwargs) from text_encoder/config.json or text_encoder_2/config.json (SD-v3)."""
+    act = cfg.get("hidden_act")
+    if act not in ("quick_gelu", "gelu"):
+        raise NotImplementedError(f"text_encoder: hidden_act = {act!r} is not implemented by the engine's plan (needs 'quick_gelu' "
+                                  "or 'gelu')")
+    arch = cfg.get("architectures")
+    if arch is not None and list(arch) != ["CLIPTextModelWithProjection"]:
+        raise NotImplementedError(f"text_encoder: only architectures = ['CLIPTextModelWithProjection'] is implemented, got {arch!r}")
+    for k in ("projection_dim", "eos_token_id"):
+        if not isinstance(cfg.get(k), int):
+            raise NotImplementedError(f"text_encoder: config value {k} = {cfg.get(k)!r} is not implemented by the engine's plan (needs an integer)")
+    heads, hidden = cfg.get("num_attention_heads"), cfg.get("hidden_size")
+    if heads is not None and hidden is not None and hidden != 64 * heads:
+        raise NotImplementedError(f"text_encoder: hidden_size = {hidden} with {heads} heads is not implemented by the engine's plan "
+                                  "(needs heads of 64)")
+    _require(cfg, "text_encoder", layer_norm_eps=1e-5, attention_dropout=0.0)
+    keys = ("vocab_size", "hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "max_position_embeddings",
+            "hidden_act", "projection_dim", "eos_token_id")
+    return {k: cfg[k] for k in keys if k in cfg}
+
+
 def t5_kwargs(cfg: dict) -> dict:
     """T5EncoderModel(**kwargs) from text_encoder_3/config.json (T5-v1.1 family, encoder-only use)."""
     if cfg.get("feed_forward_proj") != "gated-gelu":

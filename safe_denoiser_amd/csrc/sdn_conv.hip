@@ -242,7 +242,7 @@ k_conv_slab(const GemmArgs g) {
   const bool res_lds = g.res_lds != 0;
   const int CW = res_lds ? BN * 2 : CW_PAD;
   const bool lean = !g.rowgate && g.act == 0 && (res_lds || !g.residual);
-  const bool lean_gelu = false, lean_gate = false;
+  const bool lean_gelu = false, lean_gate = false, lean_erf = false;
   const __amdgpu_buffer_rsrc_t rs_res = make_rsrc(g.residual ? g.residual : g.a, g.res_bytes);
   constexpr int PASSES = 2, WM_PER_PASS = WGM / PASSES, ROWS_PER_PASS = 64 * WM_PER_PASS;
   static_assert(ROWS_PER_PASS * CW_PAD + 8 * BN * 8 <= LDS_BYTES, "staged pass and the column-sum scratch must fit the LDS");
@@ -252,7 +252,7 @@ k_conv_slab(const GemmArgs g) {
 #define SDN_PASS 1
 #include "sdn_gemm_epilogue.inc"
 #undef SDN_PASS
-  (void)lean_gelu; (void)lean_gate; (void)staged; (void)NSTAGE; (void)STAGE; (void)lean;
+  (void)lean_gelu; (void)lean_gate; (void)lean_erf; (void)staged; (void)NSTAGE; (void)STAGE; (void)lean;
 #endif  // __HIP_DEVICE_COMPILE__
 }
 

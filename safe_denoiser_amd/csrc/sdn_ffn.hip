@@ -322,7 +322,7 @@ k_ffn320(const FfnArgs a) {
   const int out_cols = BN;
   const bool res_lds = true;
   const int CW = BN * 2;
-  const bool lean = true, lean_gelu = false, lean_gate = false;
+  const bool lean = true, lean_gelu = false, lean_gate = false, lean_erf = false;
   constexpr int PASSES = 1, WM_PER_PASS = WGM / PASSES, ROWS_PER_PASS = 64 * WM_PER_PASS;
   static_assert(BM * CW_PAD <= NSTAGE * STAGE - 8 * BN * 8, "staged tile and the column-sum scratch must fit the LDS");
 #define SDN_EPI_RES_PRELOADED
@@ -332,7 +332,7 @@ k_ffn320(const FfnArgs a) {
 #undef SDN_EPI_RES_PRELOADED
   SDN_FTS_MARK(7)                                                           // trailing k-tiles + epilogue
   SDN_FTS_FLUSH
-  (void)NWAVES; (void)WGM; (void)lean_gelu; (void)lean_gate; (void)staged; (void)CW_PAD; (void)KT2;
+  (void)NWAVES; (void)WGM; (void)lean_gelu; (void)lean_gate; (void)lean_erf; (void)staged; (void)CW_PAD; (void)KT2;
 #endif  // __HIP_DEVICE_COMPILE__
 }
 

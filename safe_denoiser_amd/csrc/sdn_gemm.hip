@@ -496,6 +496,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g) {
   const int CW = res_lds ? BN * 2 : CW_PAD;
   const bool lean = staged && !g.rowgate && g.act == 0 && (res_lds || !g.residual);
   const bool lean_gelu = staged && !g.rowgate && g.act == 3 && !g.residual;
+  const bool lean_erf = g.act == SDN_ACT_GELU;               // (the host admits it as a staged 16-bit output with no gate / residual only)
   const bool lean_gate = staged && g.rowgate && g.act == 0 && res_lds;
   const __amdgpu_buffer_rsrc_t rs_res = make_rsrc(g.residual ? g.residual : g.a, g.res_bytes);
   // the staged tile may exceed the LDS (256 x 320): stage PASSES groups of wave-rows one after the other
@@ -774,7 +775,11 @@ static int sdn_gemm_impl(int dtype, const sdn_gemm_desc* d, const void* a, const
   } else {
     return SDN_E_INVALID;
   }
-  if (d->act < 0 || d->act > 4 || d->out_kind < 0 || d->out_kind > 2) return SDN_E_INVALID;
+  if (d->act < 0 || (d->act > 4 && d->act != SDN_ACT_GELU) || d->out_kind < 0 || d->out_kind > 2) return SDN_E_INVALID;
+  // exact-erf GELU: the lean staged epilogue and nothing else (whole-width 16-bit rows, nothing added after the activation)
+  if (d->act == SDN_ACT_GELU && (x3 || d->out_kind != SDN_OUT_BF16 || n_valid != d->N || rowgate || residual || d->split_k > 1 || partials ||
+                                 ln_c || ln_d || col_stats))
+    return SDN_E_INVALID;
   if (d->act == SDN_ACT_GEGLU && ((d->out_kind != SDN_OUT_BF16 && !x3) || rowbias || rowgate || residual || n_valid != d->N))
     return SDN_E_INVALID;
   if ((rowbias || rowgate || d->residual_bcast || d->out_kind == SDN_OUT_F32_NCHW) && d->rows_per_batch <= 0) return SDN_E_INVALID;

@@ -205,6 +205,16 @@
         uint2 pk; pk.x = T::pack2(gelu_tanh(v[0]), gelu_tanh(v[1])); pk.y = T::pack2(gelu_tanh(v[2]), gelu_tanh(v[3]));
         *reinterpret_cast<uint2*>(slot0 + i * 16 * CW_PAD + j * 32) = pk;
       }
+  } else if (lean_erf) {                                      // 16-bit staged output of erf-GELU (OpenCLIP bigG's MLP)
+    unsigned char* slot0 = smem + ((wm % WM_PER_PASS) * 64 + fr) * CW_PAD + (wn * 16 * NREP + fq * 4) * 2;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < NREP; ++j) {
+        const f32x4 v = acc[i][j];
+        uint2 pk; pk.x = T::pack2(gelu_erf(v[0]), gelu_erf(v[1])); pk.y = T::pack2(gelu_erf(v[2]), gelu_erf(v[3]));
+        *reinterpret_cast<uint2*>(slot0 + i * 16 * CW_PAD + j * 32) = pk;
+      }
   } else if (lean_gate) {                                     // adaLN-zero: out = residual + gate[sample] * (acc)
     unsigned char* slot0 = smem + ((wm % WM_PER_PASS) * 64 + fr) * (BN * 2) + (wn * 16 * NREP + fq * 4) * 2;
 #pragma unroll

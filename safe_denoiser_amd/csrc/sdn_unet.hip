@@ -40,7 +40,7 @@ struct Ref { int space = SP_NONE; int64_t off = 0; };
 
 enum OpKind { OP_TEMB, OP_CONV_IN, OP_GEMM, OP_GN, OP_LN, OP_ATTN, OP_PATCHIFY, OP_UNPATCHIFY, OP_LATENT_MIX, OP_SOFTMAX,
               OP_TRANSPOSE, OP_GAUSS, OP_REPEAT, OP_CLIP_EMBED, OP_MATTN, OP_ROWSTATS, OP_FFN, OP_SPLIT3,
-              OP_RMSNORM, OP_EMBED, OP_T5_BIAS, OP_BATTN };
+              OP_RMSNORM, OP_EMBED, OP_T5_BIAS, OP_BATTN, OP_EOS_ROWS, OP_COPY_ROWS };
 
 struct Op {
   int kind;
@@ -54,6 +54,7 @@ struct Op {
   int x3t = 0;               // bf16x3 plan: this GEMM runs on sdn_gemm_bf16 over triple operands (gd holds the EXPANDED K / Cin)
   int pair_in = 0;           // bf16x3 plan: attention whose q / k / v are column blocks of ONE hi | lo pair-row buffer (sdn_attention_x3_pairs)
   int tri_out = 0;           // bf16x3 plan: GroupNorm / LayerNorm / attention write the bf16 hi|lo|hi triple a GEMM will read
+  int dyn_ldc = 0;           // projected CLIP plan: the output's leading dimension is the caller's row stride of this forward
   int n1 = 0, mod = 0, ld_mod = 0, patch = 0;
   // GN / LN / conv_in / attention scalars
   int batch = 0, hw = 0, c1 = 0, c2 = 0, groups = 0, silu = 0;
@@ -137,6 +138,9 @@ struct sdn_unet {
   bool is_clip = false;
   sdn_clip_config ccfg;
   const void* clip_mask = nullptr;      // key-padding mask of the forward in flight (nullable; CLIP and T5)
+  bool is_clip_proj = false;            // CLIPTextModelWithProjection: is_clip as well (same layers), ccfg mirrors pcfg
+  sdn_clip_proj_config pcfg;
+  int64_t proj_hbs = 0, proj_hrs = 0, proj_ers = 0;   // output strides (elements) of the sdn_clip_proj_forward in flight
   bool is_t5 = false;
   sdn_t5_config tcfg;
   std::vector<sdn_param_info> params;
@@ -1293,6 +1297,8 @@ struct Builder {
     Act x = act(rows, C, n, 0);
     { Op o; o.kind = OP_CLIP_EMBED; o.a = Ref{SP_LATENTS, 0}; o.w = tok; o.bias = pos; o.out = R(x); o.rows = rows; o.hw = n; o.c1 = C;
       o.c2 = c.vocab_size; o.bytes = 6.0 * rows * C; snprintf(o.label, sizeof(o.label), "k_clip_embed"); plan->ops.push_back(o); }
+    const bool proj = u->is_clip_proj;
+    const int mlp_act = proj ? u->pcfg.act : SDN_ACT_QUICK_GELU;
     char buf[96];
     for (int l = 0; l < c.num_layers; ++l) {
       snprintf(buf, sizeof(buf), "encoder.layers.%d", l);
@@ -1320,13 +1326,33 @@ struct Builder {
       drop(at); drop(x);
       layernorm(x2, l2g, l2b, ln);
       Act h = act(rows, I, n, 0);
-      gemm(rows, I, C, R(ln), f1w, f1b, R(h), SDN_ACT_QUICK_GELU);
+      gemm(rows, I, C, R(ln), f1w, f1b, R(h), mlp_act);
       drop(ln);
       x = act(rows, C, n, 0);
       gemm(rows, C, I, R(h), f2w, f2b, R(x), SDN_ACT_NONE, R(x2));
       drop(h); drop(x2);
+      if (proj && l == c.num_layers - u->pcfg.hidden_tap) {
+        // hidden_states[-hidden_tap]: this layer's output as it is (no final norm), into the caller's strided slice
+        Op o; o.kind = OP_COPY_ROWS; o.a = R(x); o.out = Ref{SP_OUT, 0}; o.batch = B; o.hw = n; o.c1 = C;
+        o.bytes = 2.0 * es * rows * C; snprintf(o.label, sizeof(o.label), "k_copy_rows"); plan->ops.push_back(o);
+      }
     }
     Ref fg = param("final_layer_norm.weight", SDN_P_VEC_F32, C, 0), fb = param("final_layer_norm.bias", SDN_P_VEC_F32, C, 0);
+    if (proj) {
+      // text_embeds = text_projection(final_layer_norm(last)[pooling position]): the norm runs on B rows, not B x 77
+      const int P = u->pcfg.projection_dim;
+      Ref tpw = param("text_projection.weight", SDN_P_MAT, P, C);
+      Act pooled = act(B, C, 1, 0);
+      { Op o; o.kind = OP_EOS_ROWS; o.a = Ref{SP_LATENTS, 0}; o.k = R(x); o.w = fg; o.bias = fb; o.out = R(pooled); o.batch = B; o.hw = n;
+        o.c1 = C; o.c2 = c.vocab_size; o.eps = 1e-5f; o.bytes = 2.0 * es * B * C + 4.0 * rows;
+        snprintf(o.label, sizeof(o.label), "k_clip_eos_rows"); plan->ops.push_back(o); }
+      drop(x);
+      gemm(B, P, C, R(pooled), tpw, Ref(), Ref{SP_POOLED, 0});
+      plan->ops.back().dyn_ldc = 1;
+      drop(pooled);
+      plan->ws_bytes = arena.peak;
+      return;
+    }
     { Op o; o.kind = OP_LN; o.a = R(x); o.rows = rows; o.c1 = C; o.eps = 1e-5f; o.w = fg; o.bias = fb; o.out = Ref{SP_OUT, 0};
       o.bytes = 4.0 * rows * C; snprintf(o.label, sizeof(o.label), "k_layernorm"); plan->ops.push_back(o); }
     drop(x);
@@ -1562,6 +1588,31 @@ int sdn_clip_create(const sdn_clip_config* cfg, sdn_unet** out) {
 int sdn_clip_forward(sdn_unet* m, const void* weights, const int32_t* input_ids, const int32_t* attention_mask,
                      void* last_hidden_state, int32_t batch, void* workspace, size_t workspace_bytes, void* stream);
 
+int sdn_clip_proj_create(const sdn_clip_proj_config* cfg, sdn_unet** out) {
+  if (!cfg || !out) return SDN_E_INVALID;
+  // widths: the CLIP plan's rules with the ceiling at bigG's 1280 (the widest size the tests run)
+  if (cfg->vocab_size <= 0 || cfg->hidden_size <= 0 || cfg->hidden_size % 128 != 0 || cfg->hidden_size > 1280 ||
+      cfg->intermediate_size <= 0 || cfg->intermediate_size % 128 != 0 || cfg->num_layers <= 0 || cfg->num_heads <= 0 ||
+      cfg->hidden_size != 64 * cfg->num_heads || cfg->max_position_embeddings <= 0 || cfg->max_position_embeddings > 4096 ||
+      cfg->dtype < 0 || cfg->dtype > 3 || cfg->projection_dim <= 0 || cfg->projection_dim % 32 != 0 ||
+      (cfg->act != SDN_ACT_QUICK_GELU && cfg->act != SDN_ACT_GELU) || cfg->eos_token_id < 0 || cfg->hidden_tap < 1 ||
+      cfg->hidden_tap > cfg->num_layers)
+    return SDN_E_INVALID;
+  sdn_unet* u = new sdn_unet();
+  memset(&u->cfg, 0, sizeof(u->cfg));
+  u->cfg.dtype = cfg->dtype;
+  if (cfg->dtype >= 2) { u->gn_fuse = false; u->ln_fold = false; u->ff_fuse = false; }   // fp32-storage modes: the plain operator chain
+  u->pcfg = *cfg;
+  u->ccfg.vocab_size = cfg->vocab_size; u->ccfg.hidden_size = cfg->hidden_size; u->ccfg.intermediate_size = cfg->intermediate_size;
+  u->ccfg.num_layers = cfg->num_layers; u->ccfg.num_heads = cfg->num_heads; u->ccfg.max_position_embeddings = cfg->max_position_embeddings;
+  u->ccfg.dtype = cfg->dtype;
+  u->is_clip = true;
+  u->is_clip_proj = true;
+  get_plan(u, 1);
+  *out = u;
+  return SDN_OK;
+}
+
 int sdn_t5_create(const sdn_t5_config* cfg, sdn_unet** out) {
   if (!cfg || !out) return SDN_E_INVALID;
   if (cfg->vocab_size <= 0 || cfg->d_model <= 0 || cfg->d_model % 64 != 0 || cfg->d_kv != 64 || cfg->d_ff <= 0 || cfg->d_ff % 64 != 0 ||
@@ -1686,10 +1737,25 @@ int sdn_vae_encode(sdn_unet* v, const void* weights, const float* image, float* 
 
 int sdn_clip_forward(sdn_unet* m, const void* weights, const int32_t* input_ids, const int32_t* attention_mask,
                      void* last_hidden_state, int32_t batch, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!m || !m->is_clip) return SDN_E_INVALID;
+  if (!m || !m->is_clip || m->is_clip_proj) return SDN_E_INVALID;
   m->clip_mask = attention_mask;
   return run_plan(m, weights, (const float*)input_ids, 0.f, weights /* no text operand */, nullptr, (float*)last_hidden_state,
                   batch, workspace, workspace_bytes, stream);
+}
+
+int sdn_clip_proj_forward(sdn_unet* m, const void* weights, const int32_t* input_ids, void* hidden, int64_t hidden_batch_stride,
+                          int64_t hidden_row_stride, void* text_embeds, int64_t embeds_row_stride, int32_t batch, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  if (!m || !m->is_clip_proj || !hidden || !text_embeds) return SDN_E_INVALID;
+  const sdn_clip_proj_config& c = m->pcfg;
+  if (hidden_row_stride < c.hidden_size || hidden_batch_stride < (int64_t)c.max_position_embeddings * hidden_row_stride ||
+      embeds_row_stride < c.projection_dim || embeds_row_stride > 0x7fffffff || (hidden_row_stride & 7) || (hidden_batch_stride & 7) ||
+      (embeds_row_stride & 7) || (reinterpret_cast<uintptr_t>(hidden) & 15) || (reinterpret_cast<uintptr_t>(text_embeds) & 15))
+    return SDN_E_INVALID;
+  m->clip_mask = nullptr;
+  m->proj_hbs = hidden_batch_stride; m->proj_hrs = hidden_row_stride; m->proj_ers = embeds_row_stride;
+  return run_plan(m, weights, (const float*)input_ids, 0.f, weights /* no text operand */, text_embeds, (float*)hidden, batch,
+                  workspace, workspace_bytes, stream);
 }
 
 size_t sdn_t5_workspace_bytes(sdn_unet* m, int32_t batch, int32_t n) {
@@ -1801,6 +1867,11 @@ static int launch_ops(sdn_unet* u, Plan* p, const char* W, const char* WS, const
           break;
         case OP_GEMM:
           if (o.x3t) { rc = launch_x3t_gemm(o, P(o.a), P(o.w), (const float*)P(o.bias), (const float*)P(o.rowbias), P(o.residual), (void*)P(o.out), stream); break; }
+          if (o.dyn_ldc) {
+            sdn_gemm_desc gd = o.gd; gd.ldc = (int)u->proj_ers;
+            rc = (x3 ? sdn_gemm_x3 : sdn_gemm_f32)(&gd, P(o.a), nullptr, P(o.w), nullptr, nullptr, nullptr, nullptr, (void*)P(o.out), stream);
+            break;
+          }
           rc = (o.ln || o.gd.split_k > 1) ? SDN_E_INVALID
                : (x3 ? sdn_gemm_x3 : sdn_gemm_f32)(&o.gd, P(o.a), P(o.a2), P(o.w), (const float*)P(o.bias), (const float*)P(o.rowbias),
                                                    (const float*)P(o.rowgate), P(o.residual), (void*)P(o.out), stream);
@@ -1856,6 +1927,13 @@ static int launch_ops(sdn_unet* u, Plan* p, const char* W, const char* WS, const
         case OP_CLIP_EMBED:
           rc = sdn_clip_embed_f32((const int32_t*)P(o.a), P(o.w), P(o.bias), o.rows, o.hw, o.c1, o.c2, (void*)P(o.out), stream);
           break;
+        case OP_EOS_ROWS:
+          rc = sdn_clip_eos_rows(2, (const int32_t*)P(o.a), P(o.k), (const float*)P(o.w), (const float*)P(o.bias), o.batch, o.hw, o.c1, o.c2,
+                                 u->pcfg.eos_token_id, o.eps, (void*)P(o.out), nullptr, stream);
+          break;
+        case OP_COPY_ROWS:
+          rc = sdn_copy_rows_strided(P(o.a), o.batch, o.hw, o.c1, 4, (void*)P(o.out), u->proj_hbs, u->proj_hrs, stream);
+          break;
         case OP_MATTN:                               // 1.7 % of the encoder's FLOPs: exact f32 products in both fp32-storage modes
           rc = sdn_masked_attention_f32(P(o.a), P(o.k), P(o.v), (void*)P(o.out), (const int32_t*)u->clip_mask, 1, o.batch, o.heads,
                                         o.nq, o.hd, o.ldq, o.ldk, o.ldv, o.ldo, o.scale, stream);
@@ -1885,7 +1963,19 @@ static int launch_ops(sdn_unet* u, Plan* p, const char* W, const char* WS, const
                                  (const float*)P(o.ln_d), P(o.a2), (const float*)P(o.bias), P(o.residual), (void*)P(o.out),
                                  o.col.space != SP_NONE ? (float*)P(o.col) : nullptr, stream);
         break;
+      case OP_EOS_ROWS:
+        rc = sdn_clip_eos_rows(f16 ? 1 : 0, (const int32_t*)P(o.a), P(o.k), (const float*)P(o.w), (const float*)P(o.bias), o.batch, o.hw,
+                               o.c1, o.c2, u->pcfg.eos_token_id, o.eps, (void*)P(o.out), nullptr, stream);
+        break;
+      case OP_COPY_ROWS:
+        rc = sdn_copy_rows_strided(P(o.a), o.batch, o.hw, o.c1, 2, (void*)P(o.out), u->proj_hbs, u->proj_hrs, stream);
+        break;
       case OP_GEMM:
+        if (o.dyn_ldc) {
+          sdn_gemm_desc gd = o.gd; gd.ldc = (int)u->proj_ers;
+          rc = (f16 ? sdn_gemm_f16 : sdn_gemm_bf16)(&gd, P(o.a), nullptr, P(o.w), nullptr, nullptr, nullptr, nullptr, (void*)P(o.out), stream);
+          break;
+        }
         if (o.ln) {
           rc = (f16 ? sdn_gemm_ln_f16 : sdn_gemm_ln_bf16)(&o.gd, P(o.a), P(o.w), (const float*)P(o.ln_c), (const float*)P(o.ln_d), o.eps,
                                                           (const float*)P(o.ln_stats), (void*)P(o.out), stream);
@@ -2064,7 +2154,8 @@ static void drop_graphs(sdn_unet* u) {
 }
 
 void sdn_unet_set_split_k(sdn_unet* u, int32_t on) {
-  if (!u || u->is_t5 || u->split_k == (on != 0)) return;        // (the T5 plan's GEMMs add into an f32 stream: no split-K form)
+  if (!u || u->is_t5 || u->is_clip_proj || u->split_k == (on != 0)) return;   // (the T5 plan's GEMMs add into an f32 stream, the projected CLIP's
+                                                                              // erf-GELU is a lean epilogue only: no split-K form)
   if (!u->is_vae && (u->is_mmdit ? u->mcfg.dtype : u->cfg.dtype) >= 2) return;   // fp32-storage modes have no split-K form
   u->split_k = on != 0;
   drop_graphs(u);
