@@ -1,7 +1,7 @@
 // Building blocks of the projected CLIP text encoders (transformers CLIPTextModelWithProjection, third party; SD-v3's
 // text_encoder and text_encoder_2): the pooled row of each sequence -- gathered at the end-token position and passed through
 // final_layer_norm, the only rows of the last layer that norm is ever applied to -- and the strided copy that places the tapped
-// hidden state into a column slice of the caller's joint buffer.  The encoder layers are the CLIP plan's (sdn_unet.hip), the
+// hidden state into a column slice of the caller's joint buffer.  The encoder layers are the CLIP plan's (sdn_plan_text.hip), the
 // exact-erf GELU an epilogue of k_gemm_dma, text_projection an ordinary plan GEMM over the rows written here.
 #include <math.h>
 #include <type_traits>

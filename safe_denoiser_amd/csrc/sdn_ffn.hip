@@ -3,7 +3,7 @@
 //   out = x + [ GEGLU(LN3(h3) W1^T + b1) | h3 ] . [ Wpo W2 | Wpo ]^T + (Wpo b2 + bpo)
 //
 // i.e. LayerNorm-folded GEGLU projection (sdn_gemm_ln_*, N = 8C) followed by the FeedForward output linear already
-// contracted with the block's proj_out (two-source GEMM, K = 5C) -- what sdn_unet.hip emitted as two launches.  Between
+// contracted with the block's proj_out (two-source GEMM, K = 5C) -- what sdn_plan_unet.hip emitted as two launches.  Between
 // them sat the [M, 4C] hidden tensor: 1.34 GB written and re-read per block at B = 128 samples, and ablations of the two
 // launches (tools/bench_gemm.py, VARIANTS=0,32,16: in-loop DMA off / stores off) put 23-38 % of their time on exactly that
 // traffic and on the L2 -> LDS re-streaming of A by 20 column tiles (13.4 GB per launch, 60 % of what the L2s can deliver).

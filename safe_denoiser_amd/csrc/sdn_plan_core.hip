@@ -1,0 +1,282 @@
+// Launch planner, shared part: the parameter manifest and activation arena behind Builder, the bf16x3 operand-expansion helpers,
+// the op emitters more than one model uses (GEMM, conv3x3, GroupNorm, LayerNorm, repeat, attention), and get_plan(), which builds
+// and caches one plan per batch size.
+#include <math.h>
+
+#include "sdn_plan.h"
+
+namespace sdn_plan {
+
+// ---- parameters -------------------------------------------------------------------------------
+Ref Builder::param(const std::string& name, int kind, int rows, int cols, int rows_padded) {
+  auto it = u->param_index.find(name);
+  if (it != u->param_index.end()) return Ref{SP_W, u->params[it->second].offset};
+  sdn_param_info pi;
+  memset(&pi, 0, sizeof(pi));
+  snprintf(pi.name, sizeof(pi.name), "%s", name.c_str());
+  pi.kind = kind; pi.rows = rows; pi.cols = cols; pi.rows_padded = rows_padded > rows ? rows_padded : rows;
+  const int64_t esz = (kind == SDN_P_VEC_F32 || kind == SDN_P_GEGLU_VEC) ? 4 : es;
+  const int64_t bytes = (int64_t)pi.rows_padded * (cols > 0 ? cols : 1) * esz;
+  pi.offset = u->weight_bytes;
+  u->weight_bytes += (bytes + 255) & ~(int64_t)255;
+  u->param_index[name] = (int)u->params.size();
+  u->params.push_back(pi);
+  return Ref{SP_W, pi.offset};
+}
+// members of a stacked matrix must be byte-contiguous: their sizes are multiples of 256 B for every SD width
+Ref Builder::stacked(const std::vector<std::string>& names, int rows_each, int cols) {
+  Ref first;
+  int64_t expect = -1;
+  for (size_t i = 0; i < names.size(); ++i) {
+    Ref r = param(names[i], SDN_P_MAT, rows_each, cols);
+    if (i == 0) first = r;
+    else if (r.off != expect) { fprintf(stderr, "libsdn: stacked weight %s is not contiguous\n", names[i].c_str()); abort(); }
+    expect = r.off + (int64_t)rows_each * cols * es;
+  }
+  return first;
+}
+Ref Builder::stacked_vec(const std::vector<std::string>& names, int n_each) {
+  Ref first; int64_t expect = -1;
+  for (size_t i = 0; i < names.size(); ++i) {
+    Ref r = param(names[i], SDN_P_VEC_F32, n_each, 0);
+    if (i == 0) first = r;
+    else if (r.off != expect) { fprintf(stderr, "libsdn: stacked bias %s is not contiguous\n", names[i].c_str()); abort(); }
+    expect = r.off + (int64_t)n_each * 4;
+  }
+  return first;
+}
+Ref Builder::derived(const std::string& name, int64_t bytes) {
+  auto it = u->param_index.find(name);
+  if (it != u->param_index.end()) return Ref{SP_W, u->params[it->second].offset};
+  sdn_param_info pi; memset(&pi, 0, sizeof(pi));
+  snprintf(pi.name, sizeof(pi.name), "%s", name.c_str());
+  pi.kind = SDN_P_DERIVED; pi.rows = (int)bytes; pi.cols = 0; pi.rows_padded = (int)bytes;
+  pi.offset = u->weight_bytes;
+  u->weight_bytes += (bytes + 255) & ~(int64_t)255;
+  u->param_index[name] = (int)u->params.size();
+  u->params.push_back(pi);
+  return Ref{SP_W, pi.offset};
+}
+
+// ---- activations ------------------------------------------------------------------------------
+Act Builder::act(int64_t rows, int C, int hw, int side, int esz) {
+  const bool dflt = esz == 0;
+  if (esz == 0) esz = es;
+  Act t; t.content = rows * C * esz;
+  t.bytes = (x3t && dflt) ? rows * C * 6 : t.content;      // a default-typed slot may hold the f32 tensor or its triple
+  t.off = arena.alloc(t.bytes); t.C = C; t.hw = hw; t.side = side; return t;
+}
+// an activation a GroupNorm will read: its producer (a GEMM) also emits per-128-row-block column sums
+Act Builder::act_gn(int64_t rows, int C, int hw, int side) {
+  Act t = act(rows, C, hw, side);
+  if (u->gn_fuse && !u->split_k && hw > 0 && hw % 128 == 0) {
+    t.st_bytes = ((rows + 127) / 128) * (int64_t)C * 8;
+    t.st_off = arena.alloc(t.st_bytes);
+  }
+  return t;
+}
+void Builder::drop(Act& t) {
+  if (t.off >= 0) { arena.release(t.off, t.bytes); tri.erase(t.off); pairs.erase(t.off); }
+  if (t.st_off >= 0) arena.release(t.st_off, t.st_bytes);
+  t.off = -1; t.st_off = -1;
+}
+
+// ---- bf16x3 by operand expansion (include/sdn.h) -------------------------------------------------
+// expanded copy of an f32 weight region [rows, cols] (stacked matrices are contiguous, so w.off names the whole operand)
+Ref Builder::x3_weight(Ref w, int rows, int cols, int group) {
+  const std::string name = "x3@" + std::to_string((long long)w.off);
+  const bool fresh = u->param_index.find(name) == u->param_index.end();
+  Ref d = derived(name, (int64_t)rows * 3 * cols * 2);
+  if (fresh) { sdn_unet::FoldJob j{w.off, -1, -1, -1, d.off, -1, -1, rows, cols}; j.kind = 2; j.group = group; u->fold_jobs.push_back(j); }
+  return d;
+}
+// the triple of an f32 tensor that no producer could write in that form (a raw residual-stream tensor, a skip concatenation)
+Act Builder::split3(Ref a, Ref a2, int64_t rows, int c1, int c2, int hw, int side) {
+  Act t = act(rows, c1 + c2, hw, side);
+  Op o; o.kind = OP_SPLIT3; o.a = a; o.a2 = a2; o.rows = rows; o.c1 = c1; o.c2 = c2; o.out = R(t);
+  o.bytes = 10.0 * (double)rows * (c1 + c2);
+  snprintf(o.label, sizeof(o.label), "k_split3");
+  plan->ops.push_back(o);
+  tri.insert(t.off);
+  return t;
+}
+
+// ---- op emitters ------------------------------------------------------------------------------
+void Builder::gemm(int64_t M, int N, int K, Ref a, Ref w, Ref bias, Ref out, int act_, Ref residual,
+                   int out_kind, int n_valid, Ref a2, int K1, Ref rowbias,
+                   int rows_per_batch, int ld_rowbias) {
+  const bool forced = force_x3t_next && x3t && !x3t_hold;
+  force_x3t_next = false;
+  if ((x3t_on(a) || forced) && (act_ == SDN_ACT_NONE || act_ == SDN_ACT_GEGLU) && out_kind != SDN_OUT_F32_NCHW && n_valid == 0) {
+    // A' = [hi | lo | hi] (written by the producing GroupNorm / LayerNorm / attention / GEGLU epilogue, or by a split pass),
+    // W' = [hi | hi | lo]: one bf16 GEMM with three times the k loop; F32 residual, F32 (or, for GEGLU, triple) output
+    Act tmp; Ref au = a;
+    if (a.space != SP_WS || !tri.count(a.off)) { tmp = split3(a, a2, M, a2.space != SP_NONE ? K1 : K, a2.space != SP_NONE ? K - K1 : 0); au = R(tmp); }
+    Op o; o.kind = OP_GEMM; memset(&o.gd, 0, sizeof(o.gd));
+    o.x3t = 1;
+    o.gd.M = (int)M; o.gd.N = N; o.gd.K = 3 * K; o.gd.a_mode = SDN_A_PLAIN; o.gd.act = act_; o.gd.out_kind = SDN_OUT_F32;
+    const bool tri_o = triple_out_next && act_ == SDN_ACT_NONE;
+    const bool pair_o = pair_out_next && act_ == SDN_ACT_NONE && !tri_o && residual.space == SP_NONE;
+    triple_out_next = false; pair_out_next = false;
+    o.gd.x3_out = act_ == SDN_ACT_GEGLU ? 2 : (tri_o ? 3 : (pair_o ? 4 : 1)); o.gd.rows_per_batch = rows_per_batch; o.gd.ld_rowbias = ld_rowbias;
+    if (pair_o && out.space == SP_WS) pairs.insert(out.off);
+    o.a = au; o.w = x3_weight(w, N, K, K); o.bias = bias; o.rowbias = rowbias; o.residual = residual; o.out = out;
+    o.flops = 2.0 * (double)M * (double)N * (double)K;
+    o.bytes = 6.0 * ((double)M * K + (double)N * K) + 4.0 * (double)M * (act_ == SDN_ACT_GEGLU ? 0.75 * N : N) +
+              (residual.space != SP_NONE ? 4.0 * (double)M * N : 0.0);
+    snprintf(o.label, sizeof(o.label), "k_gemm<%d>x3", sdn_gemm_pick_tile((int)M, N, 3 * K, act_));
+    push_gemm(o);
+    if ((act_ == SDN_ACT_GEGLU || tri_o) && out.space == SP_WS) tri.insert(out.off);
+    if (tmp.off >= 0) drop(tmp);                            // stream order: the next op may reuse it
+    return;
+  }
+  triple_out_next = false; pair_out_next = false;
+  const bool rp = res_pre_next && residual.space != SP_NONE && act_ == SDN_ACT_NONE && out_kind == SDN_OUT_BF16 && n_valid == 0 && es == 2;
+  res_pre_next = false;
+  Op o; o.kind = OP_GEMM; memset(&o.gd, 0, sizeof(o.gd));
+  o.gd.res_pre = rp ? 1 : 0;
+  o.gd.M = (int)M; o.gd.N = N; o.gd.K = K; o.gd.a_mode = SDN_A_PLAIN; o.gd.K1 = K1; o.gd.act = act_;
+  o.gd.out_kind = out_kind; o.gd.n_valid = n_valid; o.gd.rows_per_batch = rows_per_batch; o.gd.ld_rowbias = ld_rowbias;
+  o.a = a; o.a2 = a2; o.w = w; o.bias = bias; o.rowbias = rowbias; o.residual = residual; o.out = out;
+  o.flops = 2.0 * (double)M * (double)(n_valid > 0 ? n_valid : N) * (double)K;
+  // algorithmic bytes: A + W + the output, + the residual operand when the epilogue adds one (it is read once, 16 bit)
+  o.bytes = 2.0 * ((double)M * K + (double)N * K + (double)M * (act_ == SDN_ACT_GEGLU ? N / 2 : N)) +
+            (residual.space != SP_NONE ? 2.0 * (double)M * N : 0.0);
+  snprintf(o.label, sizeof(o.label), "k_gemm<%d>%s", sdn_gemm_pick_tile((int)M, N, K, act_, residual.space != SP_NONE && !rp), rp ? "/rp" : "");
+  push_gemm(o);
+}
+// Small-M / long-K GEMMs (one-prompt batches) run in split-K form: the partial buffer lives only for this op.
+void Builder::push_gemm(Op& o) {
+  o.col = pending_cols; pending_cols = Ref();
+  const int nv = o.gd.n_valid > 0 ? o.gd.n_valid : o.gd.N;
+  const int split = (!u->split_k || nv != o.gd.N) ? 1 : sdn_gemm_pick_split(o.gd.M, o.gd.N, o.gd.K, o.gd.act, o.gd.out_kind);
+  if (split > 1) {
+    const int64_t bytes = (int64_t)split * o.gd.M * o.gd.N * 4;
+    const int64_t off = arena.alloc(bytes);
+    o.gd.split_k = split; o.aux = Ref{SP_WS, off}; o.rows = bytes;
+    arena.release(off, bytes);                              // stream order: the next op may reuse it
+    const size_t L = strlen(o.label);
+    if (L + 3 < sizeof(o.label)) snprintf(o.label + L, sizeof(o.label) - L, "/s%d", split);
+  }
+  plan->ops.push_back(o);
+  plan->flops += o.flops;
+}
+void Builder::conv3x3(const Act& in, int cout, int n_pad, Ref w, Ref bias, Ref out, int stride, int upsample, Ref residual,
+                      Ref rowbias, int ld_rowbias, int out_kind, int n_valid, int asym_pad) {
+  const int Hi = upsample ? in.side * 2 : in.side;
+  const int Ho = (Hi + (asym_pad ? 1 : 2) - 3) / stride + 1;
+  if (x3t_on(R(in))) {
+    // the same convolution over an input with 3 Cin channels per pixel ([hi | lo | hi]) and per-tap weights [hi | hi | lo]
+    Act tmp; Ref au = R(in);
+    if (!tri.count(in.off)) { tmp = split3(R(in), Ref(), (int64_t)B * in.side * in.side, in.C, 0, in.hw, in.side); au = R(tmp); }
+    Op o; o.kind = OP_GEMM; memset(&o.gd, 0, sizeof(o.gd));
+    o.x3t = 1;
+    o.gd.M = B * Ho * Ho; o.gd.N = n_pad; o.gd.K = 27 * in.C; o.gd.a_mode = SDN_A_CONV3X3;
+    o.gd.Hs = in.side; o.gd.Ws = in.side; o.gd.Cin = 3 * in.C; o.gd.Ho = Ho; o.gd.Wo = Ho; o.gd.stride = stride;
+    o.gd.upsample = upsample; o.gd.asym_pad = asym_pad; o.gd.n_valid = n_valid; o.gd.rows_per_batch = Ho * Ho; o.gd.ld_rowbias = ld_rowbias;
+    if (out_kind == SDN_OUT_F32_NCHW) { o.gd.out_kind = out_kind; o.gd.x3_out = 0; }     // conv_out: the general epilogue's NCHW f32 form
+    else { o.gd.out_kind = SDN_OUT_F32; o.gd.x3_out = 1; }
+    o.a = au; o.w = x3_weight(w, n_pad, 9 * in.C, in.C); o.bias = bias; o.rowbias = rowbias; o.residual = residual; o.out = out;
+    o.flops = 2.0 * (double)o.gd.M * (double)cout * 9.0 * in.C;
+    o.bytes = 6.0 * ((double)B * in.side * in.side * in.C + (double)n_pad * 9 * in.C) + 4.0 * (double)o.gd.M * cout +
+              (residual.space != SP_NONE ? 4.0 * (double)o.gd.M * cout : 0.0);
+    if (Ho == in.side && sdn_conv_slab_shape_ok(o.gd.M, n_pad, 3 * in.C, in.side, stride, upsample, asym_pad, SDN_OUT_BF16, n_valid) &&
+        sdn_gemm_pick_tile(o.gd.M, n_pad, o.gd.K, SDN_ACT_NONE) == 10)
+      snprintf(o.label, sizeof(o.label), "k_conv_slab<%d>/x3", in.side);
+    else
+      snprintf(o.label, sizeof(o.label), "k_gemm<%d>x3", sdn_gemm_pick_tile(o.gd.M, n_pad, o.gd.K, SDN_ACT_NONE));
+    push_gemm(o);
+    if (tmp.off >= 0) drop(tmp);
+    return;
+  }
+  Op o; o.kind = OP_GEMM; memset(&o.gd, 0, sizeof(o.gd));
+  o.gd.res_pre = (res_pre_next && residual.space != SP_NONE && out_kind == SDN_OUT_BF16 && n_valid == 0 && es == 2) ? 1 : 0;
+  res_pre_next = false;
+  o.gd.M = B * Ho * Ho; o.gd.N = n_pad; o.gd.K = 9 * in.C; o.gd.a_mode = SDN_A_CONV3X3;
+  o.gd.Hs = in.side; o.gd.Ws = in.side; o.gd.Cin = in.C; o.gd.Ho = Ho; o.gd.Wo = Ho; o.gd.stride = stride;
+  o.gd.upsample = upsample; o.gd.asym_pad = asym_pad; o.gd.out_kind = out_kind; o.gd.n_valid = n_valid; o.gd.rows_per_batch = Ho * Ho;
+  o.gd.ld_rowbias = ld_rowbias;
+  o.a = R(in); o.w = w; o.bias = bias; o.rowbias = rowbias; o.residual = residual; o.out = out;
+  o.flops = 2.0 * (double)o.gd.M * (double)cout * (double)o.gd.K;
+  o.bytes = 2.0 * ((double)B * in.side * in.side * in.C + (double)n_pad * o.gd.K + (double)o.gd.M * cout) +
+            (residual.space != SP_NONE ? 2.0 * (double)o.gd.M * cout : 0.0);      // + the residual map the epilogue adds
+  if (Ho == in.side && sdn_conv_slab_shape_ok(o.gd.M, n_pad, in.C, in.side, stride, upsample, asym_pad, out_kind, n_valid) &&
+      sdn_gemm_pick_tile(o.gd.M, n_pad, o.gd.K, SDN_ACT_NONE) == 10)
+    snprintf(o.label, sizeof(o.label), "k_conv_slab<%d>", in.side);
+  else
+    snprintf(o.label, sizeof(o.label), "k_gemm<%d>", sdn_gemm_pick_tile(o.gd.M, n_pad, o.gd.K, SDN_ACT_NONE));
+  push_gemm(o);
+}
+void Builder::groupnorm(const Act& x, const Act* x2, float eps, int silu, Ref gamma, Ref beta, const Act& out) {
+  Op o; o.kind = OP_GN; o.a = R(x); if (x2) o.a2 = R(*x2);
+  o.batch = B; o.hw = x.hw; o.c1 = x.C; o.c2 = x2 ? x2->C : 0; o.groups = u->cfg.norm_groups; o.eps = eps;
+  o.silu = silu; o.w = gamma; o.bias = beta; o.out = R(out); o.aux = gn_stats;
+  if (x3t) { o.tri_out = 1; tri.insert(out.off); }            // every GroupNorm of the UNet feeds a conv / linear
+  if (x.st_off >= 0 && (!x2 || x2->st_off >= 0)) {             // statistics come with the inputs: apply pass only
+    o.cols1 = Ref{SP_WS, x.st_off};
+    if (x2) o.cols2 = Ref{SP_WS, x2->st_off};
+  }
+  o.bytes = 2.0 * (o.cols1.space != SP_NONE ? 2.0 : 3.0) * (double)B * x.hw * (o.c1 + o.c2);   // reads (stats?, apply) + one write
+  snprintf(o.label, sizeof(o.label), o.cols1.space != SP_NONE ? "k_gn_apply" : "k_gn_stats+apply");
+  plan->ops.push_back(o);
+}
+void Builder::layernorm(const Act& x, Ref gamma, Ref beta, const Act& out) {
+  Op o; o.kind = OP_LN; o.a = R(x); o.rows = (int64_t)B * x.hw; o.c1 = x.C; o.eps = 1e-5f; o.w = gamma; o.bias = beta;
+  o.out = R(out);
+  if (x3t) { o.tri_out = 1; tri.insert(out.off); }            // ... and every LayerNorm a projection
+  o.bytes = 2.0 * 2.0 * (double)o.rows * x.C;
+  snprintf(o.label, sizeof(o.label), "k_layernorm");
+  plan->ops.push_back(o);
+}
+void Builder::repeat(const Act& in, const Act& out, int rep) {          // out = cat([in] * rep) along the batch
+  Op o; o.kind = OP_REPEAT; o.a = R(in); o.out = R(out); o.rows = in.content; o.c1 = rep;     // (stream tensors: never triples)
+  o.bytes = (double)in.content * (1 + rep);
+  snprintf(o.label, sizeof(o.label), "k_repeat");
+  plan->ops.push_back(o);
+}
+void Builder::attention(Ref q, Ref k, Ref v, Ref out, int nq, int nk, int C, int ldq, int ldk, int ldv, bool kv_pairs) {
+  Op o; o.kind = OP_ATTN; o.a = q; o.k = k; o.v = v; o.out = out; o.batch = B; o.heads = u->cfg.n_heads;
+  o.nq = nq; o.nk = nk; o.hd = C / u->cfg.n_heads; o.ldq = ldq; o.ldk = ldk; o.ldv = ldv; o.ldo = C;
+  o.scale = 1.0f / sqrtf((float)o.hd);
+  if (x3t && out.space == SP_WS) { o.tri_out = 1; tri.insert(out.off); }   // its only reader is the to_out projection
+  if (q.space == SP_WS && pairs.count(q.off)) {               // 1: q / k / v = column blocks of ONE pair-row buffer (self-attention);
+    o.pair_in = kv_pairs ? 2 : 1; pairs.erase(q.off);         // 2: q = [hi(C) | lo(C)], k / v = column blocks of the text projection's pair rows
+  } else if (kv_pairs) {
+    plan_bad = true;                                          // K / V were written as pairs but Q was not: refuse the plan (forward rejects it)
+  }
+  const double f = 4.0 * (double)B * o.heads * (double)nq * (double)nk * (double)o.hd;
+  o.flops = f;
+  o.bytes = 2.0 * (double)B * C * (2.0 * nq + 2.0 * nk);
+  snprintf(o.label, sizeof(o.label), "k_attn<%d>", o.hd);
+  plan->ops.push_back(o);
+  plan->flops += f; plan->attn_flops += f;
+}
+
+Plan* get_plan(sdn_unet* u, int batch, int n) {
+  if (u->kind == T5 && n == 0) n = 512;
+  const int key = u->kind == T5 ? batch * 1024 + n : batch;
+  auto it = u->plans.find(key);
+  if (it != u->plans.end()) return &it->second;
+  if (u->kind == T5 && u->plans.size() >= 64) {                      // ragged lengths: bounded cache (no forward is in flight on the host side)
+    u->plans.clear();
+    u->profiled_batch = 0;                                      // ... and a profiled forward's plan is gone with it: nothing left to read
+  }
+  Plan& p = u->plans[key];
+  p.batch = batch;
+  Builder b{u, &p};
+  b.B = batch;
+  b.seq = n;
+  b.es = u->dtype() >= 2 ? 4 : 2;                               // fp32 storage: SD-v1.4 UNet, CLIP and MMDiT plans
+  b.x3t = u->kind == UNET && u->dtype() == 3 && u->x3_expand;
+  switch (u->kind) {
+    case UNET: b.build(); break;
+    case MMDIT: b.build_mmdit(); break;
+    case VAE_DECODER: b.build_vae(); break;
+    case VAE_ENCODER: b.build_vae_encoder(); break;
+    case CLIP: case CLIP_PROJ: b.build_clip(); break;
+    case T5: b.build_t5(); break;
+  }
+  return &p;
+}
+
+}  // namespace sdn_plan

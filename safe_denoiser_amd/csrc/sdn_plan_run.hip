@@ -1,0 +1,429 @@
+// Launch planner, execution: the interpreter that launches a plan's ops (one function per storage class), the chunked GEMM launch of
+// the bf16x3 plan, run_plan() with hipGraph capture / replay and text K / V reuse, and the readers of a profiled forward.
+#include "sdn_plan.h"
+
+namespace sdn_plan {
+
+const char* resolve(const Ref& r, const char* w, const char* ws, const char* lat, const char* text, const char* out,
+                    const char* pooled, const char* kv) {
+  switch (r.space) {
+    case SP_W: return w + r.off;
+    case SP_WS: return ws + r.off;
+    case SP_KV: return kv + r.off;
+    case SP_LATENTS: return lat + r.off;
+    case SP_TEXT: return text + r.off;
+    case SP_OUT: return out + r.off;
+    case SP_POOLED: return pooled + r.off;
+    default: return nullptr;
+  }
+}
+
+// A GEMM of the bf16x3 plan on sdn_gemm_bf16 (triple operands, expanded weights).  The LDS-DMA tiles address each operand with
+// 31-bit byte offsets, and a triple is 1.5 x its f32 tensor: the launch is cut into row chunks (whole samples for a conv) that
+// stay below 2 GiB per operand.  Rows are independent, so the chunks are the same arithmetic.
+static long g_x3_chunk_limit = (1L << 31) - 4096;      // bytes of A operand per launch (tests lower it: sdn_debug_set_x3_chunk_bytes)
+extern "C" void sdn_debug_set_x3_chunk_bytes(long long bytes) { g_x3_chunk_limit = bytes > 0 ? (long)bytes : (1L << 31) - 4096; }
+
+static int launch_x3t_gemm(const Op& o, const char* a, const char* w, const float* bias, const float* rowbias, const char* residual,
+                           void* out, void* stream) {
+  const sdn_gemm_desc& d = o.gd;
+  const bool conv = d.a_mode == SDN_A_CONV3X3;
+  const long rows_out_unit = conv ? (long)d.Ho * d.Wo : 256;                 // chunk granularity in output rows
+  const long a_bytes_unit = conv ? (long)d.Hs * d.Ws * d.Cin * 2 : 256L * d.K * 2;
+  const long units = conv ? d.M / rows_out_unit : (d.M + 255) / 256;
+  long per = g_x3_chunk_limit / a_bytes_unit;                                 // units per launch
+  if (per < 1) return SDN_E_INVALID;
+  if (per > units) per = units;
+  if (per < units) {
+    // More than one launch: EQUAL chunks that are whole waves of tiles where the operand allows it.  "As many units as fit, then the
+    // rest" gave 192 samples of a 960-channel 64^2 conv as 91 + 91 + 10 (6 + 6 + 1 waves of 256-row tiles on 256 CUs against 12 for
+    // the rows themselves) and the 3072 row blocks of FF2 at 64^2 as 1092 + 1092 + 888 (5 + 5 + 4); 64 + 64 + 64 and 3 x 1024 are 12.
+    const long n = (units + per - 1) / per;
+    long even = (units + n - 1) / n;
+    const int nrep = sdn_gemm_pick_tile((int)(even * rows_out_unit < d.M ? even * rows_out_unit : d.M), d.N, d.K, d.act, 0);
+    const long tile_rows = nrep >= 8 ? 256 : 128, tile_cols = 32L * (nrep > 0 ? nrep : 2);
+    const long tiles_per_unit = ((rows_out_unit + tile_rows - 1) / tile_rows) * ((d.N + tile_cols - 1) / tile_cols);
+    long a_ = 256, b_ = tiles_per_unit % 256;                                 // q = units per whole wave of 256 tiles = 256 / gcd(256, tiles_per_unit)
+    while (b_) { const long t_ = a_ % b_; a_ = b_; b_ = t_; }
+    const long q = 256 / a_;
+    const long aligned = (even + q - 1) / q * q;
+    if (aligned <= per) even = aligned;
+    per = even;
+  }
+  const int n_cols = d.x3_out == 2 ? d.N / 2 : d.N;                           // logical output width
+  const long out_row_bytes = d.x3_out == 0 ? 0 : ((d.x3_out == 1 || d.x3_out == 4) ? 4L * n_cols : 6L * n_cols);
+  if (d.x3_out == 0 && per < units) return SDN_E_INVALID;                     // (the NCHW output of conv_out is not chunked: 4 channels)
+  for (long u0 = 0; u0 < units; u0 += per) {
+    const long nu = units - u0 < per ? units - u0 : per;
+    sdn_gemm_desc c = d;
+    const long r0 = u0 * rows_out_unit;
+    long rn = nu * rows_out_unit;
+    if (r0 + rn > d.M) rn = d.M - r0;
+    c.M = (int)rn;
+    const float* rb = rowbias;
+    if (rowbias && d.rows_per_batch > 0) rb = rowbias + (r0 / d.rows_per_batch) * d.ld_rowbias;   // chunks start on sample boundaries when it matters (conv)
+    const int rc = sdn_gemm_bf16(&c, a + u0 * a_bytes_unit, nullptr, w, bias, rb, nullptr,
+                                 residual ? residual + r0 * 4L * n_cols : nullptr, (char*)out + r0 * out_row_bytes, stream);
+    if (rc != SDN_OK) return rc;
+  }
+  return SDN_OK;
+}
+
+// The operands of the forward in flight: P(ref) is the address a plan-time Ref names.
+struct Operands {
+  const char *W, *WS, *L, *T, *O, *PL, *KV;
+  const char* operator()(const Ref& r) const { return resolve(r, W, WS, L, T, O, PL, KV); }
+};
+
+// One op of a plan in the fp32-storage modes: same plan, fp32 operators (sdn_f32.hip); x3 = bf16x3 contractions (sdn_gemm_x3 /
+// sdn_attention_x3).  t_dev != nullptr: the timestep is read from device memory (graph mode).
+static int launch_op_f32(sdn_unet* u, const Op& o, const Operands& P, bool x3, float timestep, const float* t_dev, void* stream) {
+  int rc = SDN_OK;
+  switch (o.kind) {
+    case OP_TEMB:
+      rc = sdn_temb_f32(timestep, t_dev, o.batch, o.c1, (void*)P(o.out), stream);
+      break;
+    case OP_CONV_IN:
+      rc = sdn_conv_in_f32((const float*)P(o.a), P(o.w), (const float*)P(o.bias), o.batch, o.c1, o.hw, o.hw, o.c2, (void*)P(o.out), stream);
+      break;
+    case OP_GEMM:
+      if (o.x3t) { rc = launch_x3t_gemm(o, P(o.a), P(o.w), (const float*)P(o.bias), (const float*)P(o.rowbias), P(o.residual), (void*)P(o.out), stream); break; }
+      if (o.dyn_ldc) {
+        sdn_gemm_desc gd = o.gd; gd.ldc = (int)u->proj_ers;
+        rc = (x3 ? sdn_gemm_x3 : sdn_gemm_f32)(&gd, P(o.a), nullptr, P(o.w), nullptr, nullptr, nullptr, nullptr, (void*)P(o.out), stream);
+        break;
+      }
+      rc = (o.ln || o.gd.split_k > 1) ? SDN_E_INVALID
+           : (x3 ? sdn_gemm_x3 : sdn_gemm_f32)(&o.gd, P(o.a), P(o.a2), P(o.w), (const float*)P(o.bias), (const float*)P(o.rowbias),
+                                               (const float*)P(o.rowgate), P(o.residual), (void*)P(o.out), stream);
+      break;
+    case OP_SPLIT3:
+      rc = sdn_split3((const float*)P(o.a), (const float*)P(o.a2), o.rows, o.c1, o.c2, (void*)P(o.out), stream);
+      break;
+    case OP_GN:
+      rc = (o.tri_out ? sdn_groupnorm_f32_triple : sdn_groupnorm_f32)(P(o.a), P(o.a2), o.batch, o.hw, o.c1, o.c2, o.groups, o.eps, o.silu,
+                                                                     (const float*)P(o.w), (const float*)P(o.bias), (void*)P(o.out),
+                                                                     (float*)P(o.aux), stream);
+      break;
+    case OP_LN:
+      if (o.mod) {                                 // MMDiT adaLN: w = scale, bias = shift (per-sample rows)
+        rc = o.tri_out ? SDN_E_INVALID
+                       : sdn_layernorm_mod_f32(P(o.a), o.rows, o.c1, o.eps, (const float*)P(o.w), (const float*)P(o.bias), o.ld_mod,
+                                               o.hw, (void*)P(o.out), stream);
+        break;
+      }
+      rc = (o.tri_out ? sdn_layernorm_f32_triple : sdn_layernorm_f32)(P(o.a), o.rows, o.c1, o.eps, (const float*)P(o.w),
+                                                                      (const float*)P(o.bias), (void*)P(o.out), stream);
+      break;
+    case OP_PATCHIFY:
+      rc = sdn_patchify_f32((const float*)P(o.a), o.batch, o.c1, o.hw, o.hw, o.patch, (void*)P(o.out), stream);
+      break;
+    case OP_UNPATCHIFY:
+      rc = sdn_unpatchify_f32((const float*)P(o.a), o.batch, o.c1, o.hw, o.hw, o.patch, (float*)P(o.out), stream);
+      break;
+    case OP_ATTN:
+      if (o.pair_in == 1) {                        // ld = 2 x (qkv width) bf16 elements, lo plane = one width on
+        rc = sdn_attention_x3_pairs(P(o.a), P(o.a) + (size_t)o.ldo * 2, P(o.a) + (size_t)o.ldo * 4, o.ldq, o.ldq, (void*)P(o.out), o.batch, o.heads,
+                                    o.nq, o.nk, o.hd, 2 * o.ldq, 2 * o.ldk, 2 * o.ldv, o.ldo, o.scale, o.tri_out, stream);
+        break;
+      }
+      if (o.pair_in == 2) {                        // q rows [hi(C) | lo(C)]; k / v = column blocks 0 / C of the rows [hi(2C) | lo(2C)]
+        rc = sdn_attention_x3_pairs(P(o.a), P(o.k), P(o.k) + (size_t)o.ldo * 2, o.ldq, o.ldk, (void*)P(o.out), o.batch, o.heads,
+                                    o.nq, o.nk, o.hd, 2 * o.ldq, 2 * o.ldk, 2 * o.ldv, o.ldo, o.scale, o.tri_out, stream);
+        break;
+      }
+      if (o.n1 > 0) {                              // MMDiT joint attention over the image and text streams
+        sdn_attn_segment2 s2{P(o.q2), P(o.k2), P(o.v2), (void*)P(o.out2), o.n1, o.ldq, o.ldk, o.ldv, o.ldo};
+        rc = o.tri_out ? SDN_E_INVALID
+                       : sdn_joint_attention_f32(x3 ? 1 : 0, P(o.a), P(o.k), P(o.v), (void*)P(o.out), &s2, o.batch, o.heads, o.nq, o.hd,
+                                                 o.ldq, o.ldk, o.ldv, o.ldo, o.scale, stream);
+        break;
+      }
+      rc = (o.tri_out ? sdn_attention_x3_triple : (x3 ? sdn_attention_x3 : sdn_attention_f32))(
+          P(o.a), P(o.k), P(o.v), (void*)P(o.out), o.batch, o.heads, o.nq, o.nk, o.hd, o.ldq, o.ldk, o.ldv, o.ldo, o.scale, stream);
+      break;
+    case OP_REPEAT:
+      rc = sdn_repeat(P(o.a), (size_t)o.rows, o.c1, (void*)P(o.out), stream);
+      break;
+    case OP_CLIP_EMBED:
+      rc = sdn_clip_embed_f32((const int32_t*)P(o.a), P(o.w), P(o.bias), o.rows, o.hw, o.c1, o.c2, (void*)P(o.out), stream);
+      break;
+    case OP_EOS_ROWS:
+      rc = sdn_clip_eos_rows(2, (const int32_t*)P(o.a), P(o.k), (const float*)P(o.w), (const float*)P(o.bias), o.batch, o.hw, o.c1, o.c2,
+                             u->pcfg.eos_token_id, o.eps, (void*)P(o.out), nullptr, stream);
+      break;
+    case OP_COPY_ROWS:
+      rc = sdn_copy_rows_strided(P(o.a), o.batch, o.hw, o.c1, 4, (void*)P(o.out), u->proj_hbs, u->proj_hrs, stream);
+      break;
+    case OP_MATTN:                               // 1.7 % of the encoder's FLOPs: exact f32 products in both fp32-storage modes
+      rc = sdn_masked_attention_f32(P(o.a), P(o.k), P(o.v), (void*)P(o.out), (const int32_t*)u->clip_mask, 1, o.batch, o.heads,
+                                    o.nq, o.hd, o.ldq, o.ldk, o.ldv, o.ldo, o.scale, stream);
+      break;
+    default:
+      rc = SDN_E_INVALID;
+  }
+  return rc;
+}
+
+// One op of a plan in the 16-bit storage modes (bf16, or f16 when `f16`).
+static int launch_op_16(sdn_unet* u, const Op& o, const Operands& P, bool f16, float timestep, const float* t_dev, void* stream) {
+  int rc = SDN_OK;
+  switch (o.kind) {
+    case OP_TEMB:
+      if (t_dev) rc = sdn_temb_from_device(f16 ? 1 : 0, t_dev, o.batch, o.c1, (void*)P(o.out), stream);
+      else rc = (f16 ? sdn_timestep_embed_f16 : sdn_timestep_embed_bf16)(timestep, o.batch, o.c1, (void*)P(o.out), stream);
+      break;
+    case OP_CONV_IN:
+      rc = (f16 ? sdn_conv_in_f16 : sdn_conv_in_bf16)((const float*)P(o.a), P(o.w), (const float*)P(o.bias), o.batch, o.c1, o.hw, o.hw, o.c2,
+                            (void*)P(o.out), stream);
+      break;
+    case OP_ROWSTATS:
+      rc = (f16 ? sdn_row_stats_f16 : sdn_row_stats_bf16)(P(o.a), o.rows, o.c1, o.eps, (float*)P(o.out), stream);
+      break;
+    case OP_FFN:
+      rc = sdn_ffn_geglu_fused(f16 ? 1 : 0, o.rows, o.c1, P(o.a), (const float*)P(o.ln_stats), P(o.w), (const float*)P(o.ln_c),
+                               (const float*)P(o.ln_d), P(o.a2), (const float*)P(o.bias), P(o.residual), (void*)P(o.out),
+                               o.col.space != SP_NONE ? (float*)P(o.col) : nullptr, stream);
+      break;
+    case OP_EOS_ROWS:
+      rc = sdn_clip_eos_rows(f16 ? 1 : 0, (const int32_t*)P(o.a), P(o.k), (const float*)P(o.w), (const float*)P(o.bias), o.batch, o.hw,
+                             o.c1, o.c2, u->pcfg.eos_token_id, o.eps, (void*)P(o.out), nullptr, stream);
+      break;
+    case OP_COPY_ROWS:
+      rc = sdn_copy_rows_strided(P(o.a), o.batch, o.hw, o.c1, 2, (void*)P(o.out), u->proj_hbs, u->proj_hrs, stream);
+      break;
+    case OP_GEMM:
+      if (o.dyn_ldc) {
+        sdn_gemm_desc gd = o.gd; gd.ldc = (int)u->proj_ers;
+        rc = (f16 ? sdn_gemm_f16 : sdn_gemm_bf16)(&gd, P(o.a), nullptr, P(o.w), nullptr, nullptr, nullptr, nullptr, (void*)P(o.out), stream);
+        break;
+      }
+      if (o.ln) {
+        rc = (f16 ? sdn_gemm_ln_f16 : sdn_gemm_ln_bf16)(&o.gd, P(o.a), P(o.w), (const float*)P(o.ln_c), (const float*)P(o.ln_d), o.eps,
+                                                        (const float*)P(o.ln_stats), (void*)P(o.out), stream);
+        break;
+      }
+      if (o.col.space != SP_NONE && o.gd.split_k <= 1) {
+        rc = (f16 ? sdn_gemm_stats_f16 : sdn_gemm_stats_bf16)(&o.gd, P(o.a), P(o.a2), P(o.w), (const float*)P(o.bias),
+                                                              (const float*)P(o.rowbias), P(o.residual), (void*)P(o.out),
+                                                              (float*)P(o.col), stream);
+        break;
+      }
+      if (o.gd.split_k > 1) {
+        rc = (f16 ? sdn_gemm_splitk_f16 : sdn_gemm_splitk_bf16)(&o.gd, P(o.a), P(o.a2), P(o.w), (const float*)P(o.bias),
+                                                                (const float*)P(o.rowbias), (const float*)P(o.rowgate), P(o.residual),
+                                                                (void*)P(o.out), (void*)P(o.aux), (size_t)o.rows, stream);
+        break;
+      }
+      rc = (f16 ? sdn_gemm_f16 : sdn_gemm_bf16)(&o.gd, P(o.a), P(o.a2), P(o.w), (const float*)P(o.bias), (const float*)P(o.rowbias),
+                         (const float*)P(o.rowgate), P(o.residual), (void*)P(o.out), stream);
+      break;
+    case OP_GN:
+      if (o.cols1.space != SP_NONE) {
+        rc = (f16 ? sdn_groupnorm_cols_f16 : sdn_groupnorm_cols_bf16)(P(o.a), P(o.a2), o.batch, o.hw, o.c1, o.c2, o.groups, o.eps,
+                                                                      o.silu, (const float*)P(o.w), (const float*)P(o.bias),
+                                                                      (void*)P(o.out), (float*)P(o.aux), (const float*)P(o.cols1),
+                                                                      (const float*)P(o.cols2), stream);
+        break;
+      }
+      rc = (f16 ? sdn_groupnorm_f16 : sdn_groupnorm_bf16)(P(o.a), P(o.a2), o.batch, o.hw, o.c1, o.c2, o.groups, o.eps, o.silu,
+                              (const float*)P(o.w), (const float*)P(o.bias), (void*)P(o.out), (float*)P(o.aux), stream);
+      break;
+    case OP_CLIP_EMBED:
+      rc = sdn_clip_embed(f16 ? 1 : 0, (const int32_t*)P(o.a), P(o.w), P(o.bias), o.rows, o.hw, o.c1, o.c2, (void*)P(o.out), stream);
+      break;
+    case OP_MATTN:
+      rc = sdn_masked_attention(f16 ? 1 : 0, P(o.a), P(o.k), P(o.v), (void*)P(o.out), (const int32_t*)u->clip_mask, 1, o.batch,
+                                o.heads, o.nq, o.hd, o.ldq, o.ldk, o.ldv, o.ldo, o.scale, stream);
+      break;
+    case OP_RMSNORM:
+      rc = sdn_rmsnorm(f16 ? 1 : 0, P(o.a), o.mod, o.rows, o.c1, o.eps, (const float*)P(o.w), (void*)P(o.out), stream);
+      break;
+    case OP_EMBED:
+      rc = sdn_embed_tokens(f16 ? 1 : 0, (const int32_t*)P(o.a), P(o.w), o.rows, o.c1, o.c2, (float*)P(o.out), stream);
+      break;
+    case OP_T5_BIAS:
+      rc = sdn_t5_relative_bias(f16 ? 1 : 0, P(o.w), u->tcfg.num_buckets, u->tcfg.max_distance, o.heads, o.nq, (float*)P(o.out), stream);
+      break;
+    case OP_BATTN:
+      rc = sdn_bias_attention(f16 ? 1 : 0, P(o.a), P(o.k), P(o.v), (void*)P(o.out), (const float*)P(o.aux), (const int32_t*)u->clip_mask,
+                              o.batch, o.heads, o.nq, o.hd, o.ldq, o.ldk, o.ldv, o.ldo, o.scale, stream);
+      break;
+    case OP_REPEAT:
+      rc = sdn_repeat(P(o.a), (size_t)o.rows, o.c1, (void*)P(o.out), stream);
+      break;
+    case OP_LATENT_MIX:
+      rc = sdn_latent_mix((const float*)P(o.a), (const float*)P(o.w), (const float*)P(o.bias), o.batch, o.c1, o.hw,
+                          o.mod ? o.scale : timestep /* decoder: the caller's latent_scale */,
+                          (float*)P(o.out), stream);
+      break;
+    case OP_SOFTMAX:
+      rc = sdn_softmax_rows(f16 ? 1 : 0, (const float*)P(o.a), o.c1, o.rows, o.c1, o.scale, (void*)P(o.out), o.c1, stream);
+      break;
+    case OP_TRANSPOSE:
+      rc = sdn_transpose16(P(o.a), (int)o.rows, o.c1, o.ldq, (void*)P(o.out), o.ldo, stream);
+      break;
+    case OP_PATCHIFY:
+      rc = (f16 ? sdn_patchify_f16 : sdn_patchify_bf16)((const float*)P(o.a), o.batch, o.c1, o.hw, o.hw, o.patch,
+                                                        (void*)P(o.out), stream);
+      break;
+    case OP_UNPATCHIFY:
+      rc = sdn_unpatchify_f32((const float*)P(o.a), o.batch, o.c1, o.hw, o.hw, o.patch, (float*)P(o.out), stream);
+      break;
+    case OP_LN:
+      if (o.mod) {
+        rc = (f16 ? sdn_layernorm_mod_f16 : sdn_layernorm_mod_bf16)(P(o.a), o.rows, o.c1, o.eps, (const float*)P(o.w),
+                                                                    (const float*)P(o.bias), o.ld_mod, o.hw,
+                                                                    (void*)P(o.out), stream);
+        break;
+      }
+      rc = (f16 ? sdn_layernorm_f16 : sdn_layernorm_bf16)(P(o.a), o.rows, o.c1, o.eps, (const float*)P(o.w), (const float*)P(o.bias),
+                              (void*)P(o.out), stream);
+      break;
+    case OP_ATTN:
+      if (o.n1 > 0) {
+        sdn_attn_segment2 s2{P(o.q2), P(o.k2), P(o.v2), (void*)P(o.out2), o.n1, o.ldq, o.ldk, o.ldv, o.ldo};
+        rc = sdn_joint_attention(f16 ? 1 : 0, P(o.a), P(o.k), P(o.v), (void*)P(o.out), &s2, o.batch, o.heads, o.nq, o.hd,
+                                 o.ldq, o.ldk, o.ldv, o.ldo, o.scale, stream);
+        break;
+      }
+      rc = (f16 ? sdn_attention_f16 : sdn_attention_bf16)(P(o.a), P(o.k), P(o.v), (void*)P(o.out), o.batch, o.heads, o.nq, o.nk, o.hd, o.ldq,
+                              o.ldk, o.ldv, o.ldo, o.scale, stream);
+      break;
+  }
+  return rc;
+}
+
+// Launches every op of the plan on `stream`.  t_dev != nullptr: the timestep is read from device memory (graph mode).
+static int launch_ops(sdn_unet* u, Plan* p, const char* W, const char* WS, const char* L, const char* T, const char* O,
+                      const char* PL, float timestep, const float* t_dev, bool prof, void* stream, bool skip_text_kv = false) {
+  const Operands P{W, WS, L, T, O, PL, WS + p->kv_base};
+  size_t opi = 0;
+  const int sdt = u->dtype();
+  const bool f32 = sdt >= 2;                                                 // fp32-storage modes (SD-v1.4 UNet, CLIP and MMDiT plans)
+  for (const Op& o : p->ops) {
+    if (skip_text_kv && o.text_kv) { ++opi; continue; }       // its output of the previous forward stands (same text version)
+    if (prof) (void)hipEventRecord(u->ev[2 * opi], (hipStream_t)stream);
+    const int rc = f32 ? launch_op_f32(u, o, P, sdt == 3, timestep, t_dev, stream) : launch_op_16(u, o, P, sdt == 1, timestep, t_dev, stream);
+    if (prof) (void)hipEventRecord(u->ev[2 * opi + 1], (hipStream_t)stream);
+    ++opi;
+    if (rc != SDN_OK) return rc;
+  }
+  return SDN_OK;
+}
+
+int run_plan(sdn_unet* u, const void* weights, const float* latents, float timestep, const void* text,
+             const void* pooled, float* out, int32_t batch, void* workspace, size_t workspace_bytes, void* stream, int n) {
+  if (!u || !weights || !latents || !text || !out || !workspace || batch <= 0) return SDN_E_INVALID;
+  Plan* p = get_plan(u, batch, n);
+  if (p->ws_bytes < 0) return SDN_E_INVALID;                      // e.g. batch not a multiple of latent_repeat
+  if (workspace_bytes < (size_t)p->ws_bytes) return SDN_E_WORKSPACE;
+  const char* W = (const char*)weights; const char* WS = (const char*)workspace;
+  const char* L = (const char*)latents; const char* T = (const char*)text; const char* O = (const char*)out;
+  const char* PL = (const char*)pooled;
+  const bool prof = u->profile_next;
+  if (prof) {                                    // opt-in diagnostics: HIP events around every launch of this forward
+    u->profile_next = false;
+    while (u->ev.size() < 2 * p->ops.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return SDN_E_LAUNCH; u->ev.push_back(e); }
+    u->profiled_batch = batch; u->profiled_n = n;
+  }
+  hipStream_t hs = (hipStream_t)stream;
+  if (u->use_graph && !prof && (u->kind == UNET || u->kind == MMDIT) && p->tscalar_off >= 0) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(hs, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
+      // Graph mode: small batches are launch-bound (~850 launches per forward); the forward is captured once per
+      // (batch, operand addresses) and replayed.  The timestep is the only per-step scalar: it is stored to the
+      // workspace by one ordinary launch and k_temb reads it from there.
+      float* t_dev = (float*)(WS + p->tscalar_off);
+      int rc = sdn_set_scalar(t_dev, timestep, stream);
+      if (rc != SDN_OK) return rc;
+      const sdn_unet::GraphKey key{batch, weights, latents, text, pooled, out, workspace};
+      auto it = u->graphs.find(key);
+      if (it == u->graphs.end()) {
+        if (u->graphs.size() >= 16) {                          // operands keep moving: graphs do not pay, stop hoarding
+          (void)hipStreamSynchronize(hs);                      // a replay may still be executing on the launch stream
+          for (auto& kv : u->graphs) (void)hipGraphExecDestroy(kv.second);
+          u->graphs.clear();
+        }
+        hipGraph_t graph = nullptr;
+        if (!u->cap_stream && hipStreamCreateWithFlags(&u->cap_stream, hipStreamNonBlocking) != hipSuccess) return SDN_E_LAUNCH;
+        if (hipStreamBeginCapture(u->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return SDN_E_LAUNCH;
+        rc = launch_ops(u, p, W, WS, L, T, O, PL, timestep, t_dev, false, (void*)u->cap_stream);   // records, does not run
+        const hipError_t ec = hipStreamEndCapture(u->cap_stream, &graph);
+        if (rc != SDN_OK || ec != hipSuccess || !graph) { if (graph) (void)hipGraphDestroy(graph); return rc != SDN_OK ? rc : SDN_E_LAUNCH; }
+        hipGraphExec_t exec = nullptr;
+        const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        if (ei != hipSuccess || !exec) return SDN_E_LAUNCH;
+        it = u->graphs.emplace(key, exec).first;
+      }
+      u->kv_version = 0;                                       // the replay rewrites every K / V slot: nothing to reuse afterwards
+      return hipGraphLaunch(it->second, hs) == hipSuccess ? SDN_OK : SDN_E_LAUNCH;
+    }
+  }
+  // text K / V reuse (ordinary launches only: a captured graph holds a fixed op list)
+  // (only UNet plans emit text_kv ops)
+  const bool declared = u->kind == UNET && u->text_version != 0 && u->subbatch_bytes == 0;
+  const bool skip = declared && !prof && u->kv_version == u->text_version && u->kv_batch == batch && u->kv_w == weights &&
+                    u->kv_text == text && u->kv_ws == workspace;
+  const int rc_l = launch_ops(u, p, W, WS, L, T, O, PL, timestep, nullptr, prof, stream, skip);
+  if (rc_l == SDN_OK && declared) { u->kv_version = u->text_version; u->kv_batch = batch; u->kv_w = weights; u->kv_text = text; u->kv_ws = workspace; }
+  else if (!declared) u->kv_version = 0;
+  return rc_l;
+}
+
+// Configuration calls (not on the hot path) drop the cached graphs; a replay may still be in flight on whatever stream the
+// caller launched it, so the device is drained first.
+void drop_graphs(sdn_unet* u) {
+  if (u->graphs.empty()) return;
+  (void)hipDeviceSynchronize();
+  for (auto& kv : u->graphs) (void)hipGraphExecDestroy(kv.second);
+  u->graphs.clear();
+}
+
+}  // namespace sdn_plan
+
+using namespace sdn_plan;
+
+// Undeclared debug hook (tools/profile_ops.py): per-launch rows of the profiled forward, in plan order.
+// out[i*6 + {0..5}] = {ms, flops, bytes, M, N, K}; labels[i*24..] = kernel label.  Returns the op count.
+extern "C" int sdn_debug_profile_ops(sdn_unet* u, double* out, char* labels, int max_ops) {
+  if (!u || !out || !labels || u->profiled_batch <= 0) return -1;
+  Plan* p = get_plan(u, u->profiled_batch, u->profiled_n);
+  int n = 0;
+  for (size_t i = 0; i < p->ops.size() && n < max_ops; ++i, ++n) {
+    if (hipEventSynchronize(u->ev[2 * i + 1]) != hipSuccess) return -2;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, u->ev[2 * i], u->ev[2 * i + 1]) != hipSuccess) return -2;
+    const Op& o = p->ops[i];
+    out[n * 6 + 0] = ms; out[n * 6 + 1] = o.flops; out[n * 6 + 2] = o.bytes;
+    out[n * 6 + 3] = o.kind == OP_GEMM ? o.gd.M : (o.kind == OP_ATTN ? o.nq : o.rows);
+    out[n * 6 + 4] = o.kind == OP_GEMM ? o.gd.N : (o.kind == OP_ATTN ? o.nk : o.c1);
+    out[n * 6 + 5] = o.kind == OP_GEMM ? o.gd.K : (o.kind == OP_ATTN ? o.hd : o.c2);
+    memcpy(labels + n * 24, o.label, 24);
+  }
+  return n;
+}
+
+extern "C" int sdn_unet_profile_read(sdn_unet* u, sdn_profile_row* rows, int32_t max_rows) {
+  if (!u || !rows || max_rows <= 0 || u->profiled_batch <= 0) return SDN_E_INVALID;
+  Plan* p = get_plan(u, u->profiled_batch, u->profiled_n);
+  if (u->ev.size() < 2 * p->ops.size()) return SDN_E_INVALID;
+  int n = 0;
+  for (size_t i = 0; i < p->ops.size(); ++i) {
+    if (hipEventSynchronize(u->ev[2 * i + 1]) != hipSuccess) return SDN_E_LAUNCH;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, u->ev[2 * i], u->ev[2 * i + 1]) != hipSuccess) return SDN_E_LAUNCH;
+    const Op& o = p->ops[i];
+    int r = 0;
+    for (; r < n; ++r) if (strcmp(rows[r].kernel, o.label) == 0) break;
+    if (r == n) {
+      if (n == max_rows) return SDN_E_INVALID;
+      memset(&rows[r], 0, sizeof(rows[r]));
+      snprintf(rows[r].kernel, sizeof(rows[r].kernel), "%s", o.label);
+      ++n;
+    }
+    rows[r].launches += 1; rows[r].ms += ms; rows[r].flops += o.flops; rows[r].bytes += o.bytes;
+  }
+  return n;
+}

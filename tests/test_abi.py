@@ -85,3 +85,65 @@ def test_registry_error_behaviour():
         repellency_methods_threshold.get_repellency_method("lsh", None, None, None, 50, 1000, 0, 0)
     with pytest.raises(NameError):
         repellency_methods_threshold.register_conditioning_method("kernel_fast")(object)
+
+
+def _small_handles(lib):
+    """One small handle of each model kind, in the order of FORWARDS below."""
+    i4 = C.c_int32 * 4
+    cfgs = [
+        (lib.sdn_unet_create, _lib.UnetConfig(in_channels=4, out_channels=4, sample_size=8, n_levels=2, block_out_channels=i4(64, 64, 0, 0),
+                                              level_has_attn=i4(1, 0, 0, 0), layers_per_block=1, n_heads=1, cross_dim=64, text_len=5,
+                                              norm_groups=32, dtype=0, latent_repeat=0)),
+        (lib.sdn_mmdit_create, _lib.MmditConfig(in_channels=16, out_channels=16, sample_size=16, patch_size=2, num_layers=3, num_heads=4,
+                                                head_dim=64, joint_dim=128, pooled_dim=64, text_len=45, time_dim=256, dtype=0)),
+        (lib.sdn_vae_decoder_create, _lib.VaeConfig(latent_channels=4, out_channels=3, sample_size=8, n_levels=2,
+                                                    block_out_channels=i4(64, 128, 0, 0), layers_per_block=1, norm_groups=32, dtype=0)),
+        (lib.sdn_vae_encoder_create, _lib.VaeConfig(latent_channels=4, out_channels=3, sample_size=8, n_levels=2,
+                                                    block_out_channels=i4(64, 128, 0, 0), layers_per_block=1, norm_groups=32, dtype=0)),
+        (lib.sdn_clip_create, _lib.ClipConfig(vocab_size=128, hidden_size=128, intermediate_size=128, num_layers=2, num_heads=2,
+                                              max_position_embeddings=77, dtype=0)),
+        (lib.sdn_clip_proj_create, _lib.ClipProjConfig(vocab_size=128, hidden_size=128, intermediate_size=128, num_layers=3, num_heads=2,
+                                                       max_position_embeddings=77, dtype=0, projection_dim=64, act=4, eos_token_id=2,
+                                                       hidden_tap=2)),
+        (lib.sdn_t5_create, _lib.T5Config(vocab_size=512, d_model=128, d_kv=64, d_ff=256, num_layers=2, num_heads=2, num_buckets=32,
+                                          max_distance=128, eps=1e-6, dtype=0)),
+    ]
+    handles = []
+    for create, cfg in cfgs:
+        h = C.c_void_p()
+        assert create(C.byref(cfg), C.byref(h)) == 0, create.__name__
+        handles.append(h)
+    return handles
+
+
+def test_entry_points_refuse_foreign_handles():
+    """Every forward entry point accepts handles of its own model kind only.  A guard that let a foreign handle through would
+    reach the plan runner, which answers SDN_E_WORKSPACE (-3) for the zero-byte workspace given here: nothing is launched."""
+    lib = sda.lib()
+    raw = C.create_string_buffer(8 * 256 + 16)
+    base = (C.addressof(raw) + 15) & ~15                        # 16-byte aligned host memory; nothing is dereferenced
+    W, X, T, P, O, E, WS = (base + 256 * i for i in range(7))
+    FORWARDS = [                                                # same order as _small_handles
+        ("sdn_unet_forward", lambda h: lib.sdn_unet_forward(h, W, X, 500.0, T, O, 1, WS, 0, None)),
+        ("sdn_mmdit_forward", lambda h: lib.sdn_mmdit_forward(h, W, X, 500.0, T, P, O, 1, WS, 0, None)),
+        ("sdn_vae_decode", lambda h: lib.sdn_vae_decode(h, W, X, 1.0, O, 1, WS, 0, None)),
+        ("sdn_vae_encode", lambda h: lib.sdn_vae_encode(h, W, X, O, 1, WS, 0, None)),
+        ("sdn_clip_forward", lambda h: lib.sdn_clip_forward(h, W, X, T, O, 1, WS, 0, None)),
+        ("sdn_clip_proj_forward", lambda h: lib.sdn_clip_proj_forward(h, W, X, O, 77 * 128, 128, E, 64, 1, WS, 0, None)),
+        ("sdn_t5_forward", lambda h: lib.sdn_t5_forward(h, W, X, T, 16, O, 1, WS, 0, None)),
+    ]
+    handles = _small_handles(lib)
+    try:
+        for i, (name, fwd) in enumerate(FORWARDS):
+            for j, h in enumerate(handles):
+                if j == i:
+                    assert fwd(h) == -3, f"{name} on its own handle must reach the plan runner"
+                else:
+                    assert fwd(h) == -1, f"{name} accepted the handle of {FORWARDS[j][0]}"
+        for j, h in enumerate(handles[:6]):
+            assert lib.sdn_t5_workspace_bytes(h, 1, 16) == 0, FORWARDS[j][0]
+            assert lib.sdn_t5_flops(h, 1, 16, None) == 0.0, FORWARDS[j][0]
+        assert lib.sdn_t5_workspace_bytes(handles[6], 1, 16) > 0 and lib.sdn_t5_flops(handles[6], 1, 16, None) > 0.0
+    finally:
+        for h in handles:
+            lib.sdn_unet_destroy(h)

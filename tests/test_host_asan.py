@@ -1,5 +1,5 @@
 """Host-side sanitizer run (SURVEY section 5 "race detection / sanitizers"): the launch-plan builder, arena allocator and
-parameter manifest (csrc/sdn_unet.hip, host code) rebuilt with -fsanitize=address,undefined (`make asan`) and driven by the
+parameter manifest (csrc/sdn_plan*.hip, host code) rebuilt with -fsanitize=address,undefined (`make asan`) and driven by the
 host-logic tests -- UNet / MMDiT / VAE / CLIP plan creation, manifests, workspace sizing, FLOP counts, argument validation of
 every entry point -- in a child process with the clang ASan runtime preloaded.  Any finding aborts the child."""
 import glob
