@@ -697,6 +697,55 @@ int sdn_clip_eos_rows(int32_t dtype, const int32_t* input_ids, const void* x, co
 int sdn_copy_rows_strided(const void* src, int32_t batch, int32_t rows_per_batch, int32_t cols, int32_t elem_bytes, void* dst,
                           int64_t dst_batch_stride, int64_t dst_row_stride, void* stream);
 
+/* ---- CLIP ViT vision tower WITH projection (the Q16 classifier's image encoder: OpenAI CLIP ViT-L/14 encode_image) ---------------
+ * Replaces `self.clip.preprocess(img)` + `clip_model.encode_image(x)` (run_nudity_sdv3.py:101-102,158-161); arithmetically
+ * transformers' CLIPVisionModelWithProjection (third party): bias-free patch convolution, class token + position embedding,
+ * pre_layrnorm (sic), pre-LN layers with bidirectional attention and a quick-GELU (or exact-erf GELU) MLP, post_layernorm on the
+ * class row, bias-free visual_projection.  Handle = sdn_unet (manifest / weights / workspace through the sdn_unet_* queries);
+ * manifest keys are transformers' without the `vision_model.` prefix -- embeddings.{class_embedding,patch_embedding.weight,
+ * position_embedding.weight}, pre_layrnorm.*, encoder.layers.N.*, post_layernorm.* -- plus `visual_projection.weight`.  The patch
+ * weight [hidden, 3, p, p] is stored flattened in (c, ky, kx) order and zero-padded to [hidden, Kpad], Kpad = 3 p^2 rounded up to
+ * 64 (588 -> 640): the convolution is sdn_clip_patch_rows followed by an ordinary plan GEMM. */
+typedef struct sdn_clip_vision_config {
+  int32_t image_size, patch_size;        /* 224, 14; image_size % patch_size == 0                      */
+  int32_t hidden_size, intermediate_size;/* 1024, 4096; both % 128 == 0, hidden <= 1280                */
+  int32_t num_layers, num_heads;         /* 24, 16 (head dim must be 64)                               */
+  int32_t projection_dim;                /* 768; % 32 == 0                                             */
+  int32_t act;                           /* SDN_ACT_QUICK_GELU (OpenAI CLIP) or SDN_ACT_GELU           */
+  int32_t dtype;                         /* 0 = bf16, 1 = fp16 storage (the reference runs this model in fp16); 2 / 3 (fp32
+                                          * storage) are refused for now */
+} sdn_clip_vision_config;
+int sdn_clip_vision_create(const sdn_clip_vision_config* cfg_host, sdn_unet** out_host);
+/* pixel_values f32 [B, 3, S, S] -> last_hidden_state [B, 1 + P, hidden] (16-bit; NULLABLE; the encoder output BEFORE
+ * post_layernorm, transformers' field of that name) and image_embeds [B, projection_dim] (16-bit).  Pointers 16-byte aligned. */
+int sdn_clip_vision_forward(sdn_unet* vision, const void* weights, const float* pixel_values, void* last_hidden_state,
+                            void* image_embeds, int32_t batch, void* workspace, size_t workspace_bytes, void* stream);
+/* its building blocks (dtype 0 = bf16, 1 = fp16):
+ * sdn_clip_patch_rows: out [B * P, kpad] 16-bit, out[(b, py, px), c * p^2 + ky * p + kx] = pixels[b, c, py * p + ky, px * p + kx]
+ *   rounded once to the storage type; columns 3 p^2 .. kpad are zero.  kpad >= 3 p^2, kpad % 8 == 0.
+ * sdn_clip_vision_embed: out[b, 0] = LN(class + pos[0]), out[b, 1 + i] = LN(patch_proj[b, i] + pos[1 + i]) for patch_proj
+ *   [B, tokens - 1, hidden] and pos [tokens, hidden] 16-bit, class / gamma / beta f32 [hidden]; the sum is formed in f32 and is NOT
+ *   rounded before the norm; two-pass f32 statistics.  hidden % 4 == 0.
+ * sdn_clip_class_rows: out[b, :] = LN(x[b, 0, :]) for x [B, seq_len, hidden] -- post_layernorm on the class rows only. */
+int sdn_clip_patch_rows(int32_t dtype, const float* pixels, int32_t batch, int32_t image_size, int32_t patch_size, int32_t kpad,
+                        void* out, void* stream);
+int sdn_clip_vision_embed(int32_t dtype, const void* patch_proj, const float* class_embedding, const void* position_embedding,
+                          const float* gamma, const float* beta, int32_t batch, int32_t tokens, int32_t hidden, float eps, void* out,
+                          void* stream);
+int sdn_clip_class_rows(int32_t dtype, const void* x, const float* gamma, const float* beta, int32_t batch, int32_t seq_len,
+                        int32_t hidden, float eps, void* out, void* stream);
+/* CLIP's image preprocessing for SQUARE uint8 images (torchvision Resize(BICUBIC) + CenterCrop + ToTensor + Normalize on a PIL
+ * image = PIL.Image.resize + an affine map):
+ * sdn_image_resize_u8: Pillow's 8-bit two-pass resampling, bit for bit.  in [B, S, S, 3] -> tmp [B, S, T, 3] (horizontal pass over
+ *   every row, rounded and clipped to uint8) -> out [B, T, T, 3] (vertical pass), all uint8 NHWC.  coeffs [T, ksize] int32 = the
+ *   taps of output index i scaled by 2^22, bounds [T, 2] int32 = (first input index, tap count <= ksize): built by the caller in
+ *   double, once per (S, T); u8 = clip((2^21 + sum px * k) >> 22, 0, 255).  Taps that would fall outside the input are not read.
+ * sdn_clip_normalize_u8: out f32 [B, 3, T, T] = ((u / 255) - mean_c) / std_c, the f32 operations in that order, of uint8 NHWC. */
+int sdn_image_resize_u8(const uint8_t* in, int32_t batch, int32_t in_size, int32_t out_size, const int32_t* coeffs,
+                        const int32_t* bounds, int32_t ksize, uint8_t* tmp, uint8_t* out, void* stream);
+int sdn_clip_normalize_u8(const uint8_t* in, int32_t batch, int32_t size, float mean_r, float mean_g, float mean_b, float std_r,
+                          float std_g, float std_b, float* out, void* stream);
+
 /* ---- T5 encoder (SD-v3 text_encoder_3: the encoder every SD-v3 SAFREE decision rests on) ---------------------------------
  * Replaces `self.text_encoder_3(input_ids, attention_mask=...)[0]` (transformers T5EncoderModel, third party), called at
  * models/sdv3/safe_denoiser_pipeline.py:316-334 (prompt embeddings), :731-768 (concept phrases) and :797-827 (one sequence per

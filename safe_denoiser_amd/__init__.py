@@ -6,5 +6,6 @@ importing works anywhere (so CPU-only tooling can inspect the package), but any 
 ``SdnUnavailable`` when the library or a gfx950 device is missing.
 """
 from ._lib import SdnUnavailable, SdnError, lib, lib_path  # noqa: F401
+from .clip_vision import CLIPVisionModelWithProjection, Q16Classifier, clip_preprocess  # noqa: F401
 
-__all__ = ["SdnUnavailable", "SdnError", "lib", "lib_path"]
+__all__ = ["SdnUnavailable", "SdnError", "lib", "lib_path", "CLIPVisionModelWithProjection", "Q16Classifier", "clip_preprocess"]

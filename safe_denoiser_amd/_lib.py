@@ -73,6 +73,11 @@ class ClipProjConfig(C.Structure):
                                          "max_position_embeddings", "dtype", "projection_dim", "act", "eos_token_id", "hidden_tap")]
 
 
+class ClipVisionConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("image_size", "patch_size", "hidden_size", "intermediate_size", "num_layers", "num_heads",
+                                         "projection_dim", "act", "dtype")]
+
+
 class T5Config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("vocab_size", "d_model", "d_kv", "d_ff", "num_layers", "num_heads", "num_buckets",
                                          "max_distance")] + [("eps", C.c_float), ("dtype", C.c_int32)]
@@ -185,6 +190,13 @@ SIGNATURES = {
     "sdn_clip_proj_forward": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i32, _vp, _sz, _vp]),
     "sdn_clip_eos_rows": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
     "sdn_copy_rows_strided": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _i64, _vp]),
+    "sdn_clip_vision_create": (C.c_int, [C.POINTER(ClipVisionConfig), C.POINTER(_vp)]),
+    "sdn_clip_vision_forward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "sdn_clip_patch_rows": (C.c_int, [_i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "sdn_clip_vision_embed": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp]),
+    "sdn_clip_class_rows": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp]),
+    "sdn_image_resize_u8": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "sdn_clip_normalize_u8": (C.c_int, [_vp, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp]),
     "sdn_t5_create": (C.c_int, [C.POINTER(T5Config), C.POINTER(_vp)]),
     "sdn_t5_workspace_bytes": (_sz, [_vp, _i32, _i32]),
     "sdn_t5_flops": (C.c_double, [_vp, _i32, _i32, C.POINTER(C.c_double)]),

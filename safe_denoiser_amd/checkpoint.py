@@ -146,6 +146,30 @@ def clip_projection_kwargs(cfg: dict) -> dict:
     return {k: cfg[k] for k in keys if k in cfg}
 
 
+def clip_vision_kwargs(cfg: dict) -> dict:
+    """CLIPVisionModelWithProjection(**kwargs) from the config.json of a transformers CLIPVisionModelWithProjection, or of a whole
+    CLIPModel (its `vision_config`, with the top-level `projection_dim`)."""
+    arch = cfg.get("architectures")
+    if arch is not None and list(arch) not in (["CLIPVisionModelWithProjection"], ["CLIPModel"]):
+        raise NotImplementedError(f"vision tower: only architectures = ['CLIPVisionModelWithProjection'] or ['CLIPModel'] are implemented, "
+                                  f"got {arch!r}")
+    if isinstance(cfg.get("vision_config"), dict):
+        cfg = {**cfg["vision_config"], **({"projection_dim": cfg["projection_dim"]} if "projection_dim" in cfg else {})}
+    act = cfg.get("hidden_act")
+    if act not in ("quick_gelu", "gelu"):
+        raise NotImplementedError(f"vision tower: hidden_act = {act!r} is not implemented by the engine's plan (needs 'quick_gelu' or 'gelu')")
+    for k in ("image_size", "patch_size", "hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "projection_dim"):
+        if not isinstance(cfg.get(k), int):
+            raise NotImplementedError(f"vision tower: config value {k} = {cfg.get(k)!r} is not implemented by the engine's plan (needs an integer)")
+    if cfg["hidden_size"] != 64 * cfg["num_attention_heads"]:
+        raise NotImplementedError(f"vision tower: hidden_size = {cfg['hidden_size']} with {cfg['num_attention_heads']} heads is not "
+                                  "implemented by the engine's plan (needs heads of 64)")
+    _require(cfg, "vision tower", layer_norm_eps=1e-5, attention_dropout=0.0, num_channels=3)
+    keys = ("image_size", "patch_size", "hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "projection_dim",
+            "hidden_act")
+    return {k: cfg[k] for k in keys}
+
+
 def t5_kwargs(cfg: dict) -> dict:
     """T5EncoderModel(**kwargs) from text_encoder_3/config.json (T5-v1.1 family, encoder-only use)."""
     if cfg.get("feed_forward_proj") != "gated-gelu":

@@ -16,7 +16,7 @@
 namespace sdn_plan {
 
 // which model a handle is: set once by its sdn_*_create, read by every entry point's guard and by get_plan
-enum ModelKind { UNET, MMDIT, VAE_DECODER, VAE_ENCODER, CLIP, CLIP_PROJ, T5 };
+enum ModelKind { UNET, MMDIT, VAE_DECODER, VAE_ENCODER, CLIP, CLIP_PROJ, T5, CLIP_VISION };
 
 enum Space { SP_NONE = 0, SP_W = 1, SP_WS = 2, SP_LATENTS = 3, SP_TEXT = 4, SP_OUT = 5, SP_POOLED = 6,
              SP_KV = 7 };   // SP_KV: the workspace's persistent tail (text K / V slots: written by one op, read by one op, never recycled)
@@ -24,7 +24,7 @@ struct Ref { int space = SP_NONE; int64_t off = 0; };
 
 enum OpKind { OP_TEMB, OP_CONV_IN, OP_GEMM, OP_GN, OP_LN, OP_ATTN, OP_PATCHIFY, OP_UNPATCHIFY, OP_LATENT_MIX, OP_SOFTMAX,
               OP_TRANSPOSE, OP_GAUSS, OP_REPEAT, OP_CLIP_EMBED, OP_MATTN, OP_ROWSTATS, OP_FFN, OP_SPLIT3,
-              OP_RMSNORM, OP_EMBED, OP_T5_BIAS, OP_BATTN, OP_EOS_ROWS, OP_COPY_ROWS };
+              OP_RMSNORM, OP_EMBED, OP_T5_BIAS, OP_BATTN, OP_EOS_ROWS, OP_COPY_ROWS, OP_PATCH_ROWS, OP_VISION_EMBED, OP_CLASS_ROWS };
 
 struct Op {
   int kind;
@@ -124,6 +124,8 @@ struct sdn_unet {
   sdn_clip_proj_config pcfg;            // CLIP_PROJ: ccfg mirrors its encoder fields (same layers as CLIP)
   int64_t proj_hbs = 0, proj_hrs = 0, proj_ers = 0;   // output strides (elements) of the sdn_clip_proj_forward in flight
   sdn_t5_config tcfg;
+  sdn_clip_vision_config vis;           // CLIP_VISION
+  bool vision_hidden = true;            // CLIP_VISION: the forward in flight was given a last_hidden_state buffer
   std::vector<sdn_param_info> params;
   std::map<std::string, int> param_index;
   int64_t weight_bytes = 0;
@@ -181,6 +183,7 @@ struct sdn_unet {
       case sdn_plan::CLIP: return ccfg.dtype;
       case sdn_plan::CLIP_PROJ: return pcfg.dtype;
       case sdn_plan::T5: return tcfg.dtype;
+      case sdn_plan::CLIP_VISION: return vis.dtype;
       default: return cfg.dtype;
     }
   }
@@ -268,6 +271,9 @@ struct Builder {
   void t5_gemm(int64_t M, int N, int K, Ref a, Ref w, Ref out, int act_, bool into_stream);
   void t5_rmsnorm(Ref x, bool x_f32, int64_t rows, int C, Ref w, Ref out);
   void build_t5();
+
+  // ---- CLIP ViT vision tower with projection (sdn_plan_vision.hip) -----------------------------------
+  void build_clip_vision();
 };
 
 // n: the sequence length of a T5 plan (ignored by every other plan); 0 = the longest one (512), which bounds the workspace of any n

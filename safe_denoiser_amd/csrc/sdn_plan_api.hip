@@ -1,4 +1,4 @@
-// Launch planner, C ABI: the seven sdn_*_create functions with their config validation, sdn_unet_prepare, the manifest / workspace /
+// Launch planner, C ABI: the sdn_*_create functions (the vision tower's is in sdn_plan_vision.hip) with their config validation, sdn_unet_prepare, the manifest / workspace /
 // FLOP queries, the forward and encode / decode entry points (each states the handle kinds it accepts), sdn_unet_set_* and the
 // undeclared debug hooks.
 #include "sdn_plan.h"
@@ -318,7 +318,7 @@ void sdn_unet_set_text_version(sdn_unet* u, uint64_t version) {
 void sdn_unet_profile_next(sdn_unet* u) { if (u) u->profile_next = true; }
 
 void sdn_unet_set_split_k(sdn_unet* u, int32_t on) {
-  if (!u || u->kind == T5 || u->kind == CLIP_PROJ || u->split_k == (on != 0)) return;   // (the T5 plan's GEMMs add into an f32 stream, the projected CLIP's
+  if (!u || u->kind == T5 || u->kind == CLIP_PROJ || u->kind == CLIP_VISION || u->split_k == (on != 0)) return;   // (the T5 plan's GEMMs add into an f32 stream, the projected CLIP's
                                                                                        // erf-GELU is a lean epilogue only: no split-K form)
   if (u->dtype() >= 2) return;                                 // fp32-storage modes have no split-K form
   set_plan_toggle(u, &sdn_unet::split_k, on != 0);             // plans are rebuilt with / without partial buffers

@@ -192,6 +192,17 @@ static int launch_op_16(sdn_unet* u, const Op& o, const Operands& P, bool f16, f
     case OP_COPY_ROWS:
       rc = sdn_copy_rows_strided(P(o.a), o.batch, o.hw, o.c1, 2, (void*)P(o.out), u->proj_hbs, u->proj_hrs, stream);
       break;
+    case OP_PATCH_ROWS:
+      rc = sdn_clip_patch_rows(f16 ? 1 : 0, (const float*)P(o.a), o.batch, o.hw, o.patch, o.c1, (void*)P(o.out), stream);
+      break;
+    case OP_VISION_EMBED:
+      rc = sdn_clip_vision_embed(f16 ? 1 : 0, P(o.a), (const float*)P(o.a2), P(o.aux), (const float*)P(o.w), (const float*)P(o.bias), o.batch,
+                                 o.hw, o.c1, o.eps, (void*)P(o.out), stream);
+      break;
+    case OP_CLASS_ROWS:
+      rc = sdn_clip_class_rows(f16 ? 1 : 0, P(o.a), (const float*)P(o.w), (const float*)P(o.bias), o.batch, o.hw, o.c1, o.eps,
+                               (void*)P(o.out), stream);
+      break;
     case OP_GEMM:
       if (o.dyn_ldc) {
         sdn_gemm_desc gd = o.gd; gd.ldc = (int)u->proj_ers;
@@ -303,6 +314,7 @@ static int launch_ops(sdn_unet* u, Plan* p, const char* W, const char* WS, const
   const bool f32 = sdt >= 2;                                                 // fp32-storage modes (SD-v1.4 UNet, CLIP and MMDiT plans)
   for (const Op& o : p->ops) {
     if (skip_text_kv && o.text_kv) { ++opi; continue; }       // its output of the previous forward stands (same text version)
+    if (o.kind == OP_COPY_ROWS && u->kind == CLIP_VISION && !u->vision_hidden) { ++opi; continue; }   // no last_hidden_state buffer was given
     if (prof) (void)hipEventRecord(u->ev[2 * opi], (hipStream_t)stream);
     const int rc = f32 ? launch_op_f32(u, o, P, sdt == 3, timestep, t_dev, stream) : launch_op_16(u, o, P, sdt == 1, timestep, t_dev, stream);
     if (prof) (void)hipEventRecord(u->ev[2 * opi + 1], (hipStream_t)stream);
