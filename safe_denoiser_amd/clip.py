@@ -3,7 +3,7 @@
 plan (sdn_clip_create / sdn_clip_forward).  SURVEY section 8f row 4.
 
 Weights: a transformers CLIPTextModel state_dict (keys with or without the `text_model.` prefix), packed once into the
-engine layout.  The tokenizer stays with the caller (its vocabulary files are not part of this engine): pass token ids.
+engine layout by EngineModel's packer (_model.py).  The tokenizer stays with the caller (its vocabulary files are not part of this engine): pass token ids.
 
 CLIPTextModelWithProjection is the SD-v3 form of the same encoder (`text_encoder` = CLIP-L, `text_encoder_2` = OpenCLIP bigG;
 models/sdv3/safe_denoiser_pipeline.py:379-386): an inner hidden state without the final norm, and the projected pooled vector
@@ -11,13 +11,12 @@ models/sdv3/safe_denoiser_pipeline.py:379-386): an inner hidden state without th
 """
 from __future__ import annotations
 
-import ctypes as C
 from types import SimpleNamespace
 
 import torch
 
 from . import _lib
-from .unet import UNet2DConditionModel
+from ._model import ALL_DTYPES, EngineModel
 
 SD14_CLIP_CONFIG = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12,
                         num_attention_heads=12, max_position_embeddings=77)
@@ -32,52 +31,26 @@ class TextEncoderOutput(tuple):
         return o
 
 
-class CLIPTextModel(UNet2DConditionModel):
+class CLIPTextModel(EngineModel):
     def __init__(self, dtype=torch.bfloat16, precision: str | None = None, **config):
         """dtype = bf16 / fp16 storage, or torch.float32 = the plan's fp32 storage mode on the f32-input matrix cores;
         precision = "bf16x3" = fp32 storage with split-operand GEMMs on the bf16 matrix cores (the UNet's tolerance-meeting
         mode).  The reference loads the text encoder in fp32 with the rest of the pipeline (run_nudity.py:277 -> load_sd(...,
         torch.float32)); its hidden states feed every cross-attention AND the SAFREE decisions (trigger-token mask, beta ->
         step count), so the fp32-storage modes are what a seed-for-seed comparison from token ids needs."""
-        if precision not in (None, "fp32", "bf16x3"):
-            raise _lib.SdnError('precision must be None, "fp32" or "bf16x3"')
-        if precision is not None:
-            dtype = torch.float32
-        if dtype not in (torch.bfloat16, torch.float16, torch.float32):
-            raise _lib.SdnError("storage dtype must be torch.bfloat16, torch.float16 or torch.float32")
-        self.dtype = dtype
-        self.precision = precision or ("fp32" if dtype == torch.float32 else None)
-        self.latent_repeat = 1
+        code = self._storage(dtype, precision, ALL_DTYPES, "storage dtype must be torch.bfloat16, torch.float16 or torch.float32")
         cfg = dict(SD14_CLIP_CONFIG)
         cfg.update(config)
         self.config = SimpleNamespace(**cfg)
         c = _lib.ClipConfig(vocab_size=cfg["vocab_size"], hidden_size=cfg["hidden_size"],
                             intermediate_size=cfg["intermediate_size"], num_layers=cfg["num_hidden_layers"],
                             num_heads=cfg["num_attention_heads"], max_position_embeddings=cfg["max_position_embeddings"],
-                            dtype=3 if self.precision == "bf16x3" else {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}[dtype])
-        h = C.c_void_p()
-        _lib.check(_lib.lib().sdn_clip_create(C.byref(c), C.byref(h)), "sdn_clip_create")
-        self._h = h
-        self._weights = None
-        self._ws = {}
-        self._read_manifest()
-
-    def state_dict_shapes(self) -> dict:
-        return {p["name"]: ((p["rows"],) if p["cols"] == 0 else (p["rows"], p["cols"])) for p in self.manifest}
-
-    @staticmethod
-    def _is_norm_param(name: str) -> bool:
-        return "norm" in name.split(".")[-2]
+                            dtype=code)
+        self._create("sdn_clip_create", c)
 
     @staticmethod
     def _canonical(sd: dict) -> dict:
         return {(k[len("text_model."):] if k.startswith("text_model.") else k): v for k, v in sd.items()}
-
-    def pack_state_dict(self, sd: dict) -> torch.Tensor:
-        return super().pack_state_dict(self._canonical(sd))
-
-    def load_state_dict(self, sd: dict, device="cuda"):
-        return super().load_state_dict(self._canonical(sd), device)
 
     def __call__(self, input_ids: torch.Tensor, attention_mask: torch.Tensor | None = None, **unused):
         _lib.require_gpu()
@@ -139,19 +112,11 @@ class CLIPTextModelWithProjection(CLIPTextModel):
         """hidden_act "quick_gelu" (CLIP-L) or "gelu" (exact erf: OpenCLIP bigG); eos_token_id 2 = transformers' legacy pooling rule
         (the highest id), else the first position holding that id; clip_skip as the reference's encode_prompt takes it: the plan
         returns hidden_states[-(clip_skip + 2)], hidden_states[-2] for None.  dtype / precision as CLIPTextModel."""
-        if precision not in (None, "fp32", "bf16x3"):
-            raise _lib.SdnError('precision must be None, "fp32" or "bf16x3"')
-        if precision is not None:
-            dtype = torch.float32
-        if dtype not in (torch.bfloat16, torch.float16, torch.float32):
-            raise _lib.SdnError("storage dtype must be torch.bfloat16, torch.float16 or torch.float32")
+        code = self._storage(dtype, precision, ALL_DTYPES, "storage dtype must be torch.bfloat16, torch.float16 or torch.float32")
         if hidden_act not in ACT_CODES:
             raise _lib.SdnError(f"hidden_act must be one of {sorted(ACT_CODES)}, got {hidden_act!r}")
         if clip_skip is not None and (not isinstance(clip_skip, int) or clip_skip < 0):
             raise _lib.SdnError("clip_skip must be None or a non-negative integer")
-        self.dtype = dtype
-        self.precision = precision or ("fp32" if dtype == torch.float32 else None)
-        self.latent_repeat = 1
         self.clip_skip = clip_skip
         self.hidden_tap = 2 if clip_skip is None else clip_skip + 2
         cfg = dict(SD14_CLIP_CONFIG)
@@ -161,30 +126,10 @@ class CLIPTextModelWithProjection(CLIPTextModel):
         c = _lib.ClipProjConfig(vocab_size=cfg["vocab_size"], hidden_size=cfg["hidden_size"],
                                 intermediate_size=cfg["intermediate_size"], num_layers=cfg["num_hidden_layers"],
                                 num_heads=cfg["num_attention_heads"], max_position_embeddings=cfg["max_position_embeddings"],
-                                dtype=3 if self.precision == "bf16x3" else {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}[dtype],
+                                dtype=code,
                                 projection_dim=projection_dim, act=ACT_CODES[hidden_act], eos_token_id=eos_token_id,
                                 hidden_tap=self.hidden_tap)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().sdn_clip_proj_create(C.byref(c), C.byref(h)), "sdn_clip_proj_create")
-        self._h = h
-        self._weights = None
-        self._ws = {}
-        self._read_manifest()
-
-    def load_state_dict(self, sd: dict, device="cuda"):
-        sd = self._canonical(sd)
-        missing = [p["name"] for p in self.manifest if p["name"] not in sd]
-        if missing:
-            raise KeyError(f"state_dict lacks {len(missing)} keys, e.g. {missing[:3]}")
-        _lib.require_gpu()
-        # tensor by tensor into the device buffer (bigG is 0.7 G parameters; device-resident state dicts stay on the device)
-        buf = torch.zeros(self.weight_bytes, dtype=torch.uint8, device=device)
-        for p in self.manifest:
-            t = sd[p["name"]].detach().to(device=device, dtype=torch.float32 if p["cols"] == 0 else self.dtype).reshape(-1).contiguous()
-            raw = t.view(torch.uint8)
-            buf[p["offset"]:p["offset"] + raw.numel()].copy_(raw)
-        self._weights = buf
-        return self._prepare()
+        self._create("sdn_clip_proj_create", c)
 
     def forward_into(self, input_ids: torch.Tensor, hidden: torch.Tensor, text_embeds: torch.Tensor):
         """Writes hidden_states[-hidden_tap] into `hidden` [B, 77, hidden_size] and text_embeds into `text_embeds` [B, projection_dim]:

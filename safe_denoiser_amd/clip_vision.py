@@ -12,7 +12,6 @@ bit from coefficient tables built here in double (resize_tables).  Non-square in
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import pickle
 from types import SimpleNamespace
@@ -22,7 +21,7 @@ import torch
 
 from . import _lib
 from .clip import ACT_CODES
-from .unet import UNet2DConditionModel
+from ._model import HALF_DTYPES, EngineModel
 
 VIT_L14_CONFIG = dict(image_size=224, patch_size=14, hidden_size=1024, intermediate_size=4096, num_hidden_layers=24,
                       num_attention_heads=16, projection_dim=768, hidden_act="quick_gelu")
@@ -186,30 +185,22 @@ def convert_openai_state_dict(sd: dict) -> dict:
     return out
 
 
-class CLIPVisionModelWithProjection(UNet2DConditionModel):
+class CLIPVisionModelWithProjection(EngineModel):
     def __init__(self, dtype=torch.float16, **config):
         """dtype = fp16 (the reference's: clip.load on a GPU) or bf16 storage; config = transformers' CLIPVisionConfig fields
         (defaults: ViT-L/14)."""
-        if dtype not in (torch.bfloat16, torch.float16):
-            raise _lib.SdnError("storage dtype must be torch.float16 or torch.bfloat16 (the fp32-storage plans are not built for this model)")
+        code = self._storage(dtype, None, HALF_DTYPES,
+                             "storage dtype must be torch.float16 or torch.bfloat16 (the fp32-storage plans are not built for this model)")
         cfg = dict(VIT_L14_CONFIG)
         cfg.update(config)
         if cfg["hidden_act"] not in ACT_CODES:
             raise _lib.SdnError(f"hidden_act must be one of {sorted(ACT_CODES)}, got {cfg['hidden_act']!r}")
-        self.dtype = dtype
-        self.precision = None
-        self.latent_repeat = 1
         self.config = SimpleNamespace(**cfg)
         c = _lib.ClipVisionConfig(image_size=cfg["image_size"], patch_size=cfg["patch_size"], hidden_size=cfg["hidden_size"],
                                   intermediate_size=cfg["intermediate_size"], num_layers=cfg["num_hidden_layers"],
                                   num_heads=cfg["num_attention_heads"], projection_dim=cfg["projection_dim"],
-                                  act=ACT_CODES[cfg["hidden_act"]], dtype={torch.bfloat16: 0, torch.float16: 1}[dtype])
-        h = C.c_void_p()
-        _lib.check(_lib.lib().sdn_clip_vision_create(C.byref(c), C.byref(h)), "sdn_clip_vision_create")
-        self._h = h
-        self._weights = None
-        self._ws = {}
-        self._read_manifest()
+                                  act=ACT_CODES[cfg["hidden_act"]], dtype=code)
+        self._create("sdn_clip_vision_create", c)
         self.num_tokens = 1 + (cfg["image_size"] // cfg["patch_size"]) ** 2
         # images of one launch plan: the GEMM tiles address an operand with 31-bit byte offsets
         widest = max(cfg["intermediate_size"], 3 * cfg["hidden_size"], self._kpad())
@@ -220,54 +211,21 @@ class CLIPVisionModelWithProjection(UNet2DConditionModel):
     def _kpad(self) -> int:
         return next(p["cols"] for p in self.manifest if p["name"] == self.PATCH_KEY)
 
-    def state_dict_shapes(self) -> dict:
+    def _source_shape(self, p: dict) -> tuple:
         ps = self.config.patch_size
-        out = {p["name"]: ((p["rows"],) if p["cols"] == 0 else (p["rows"], p["cols"])) for p in self.manifest}
-        out[self.PATCH_KEY] = (self.config.hidden_size, 3, ps, ps)
-        return out
-
-    @staticmethod
-    def _is_norm_param(name: str) -> bool:
-        return "norm" in name.split(".")[-2]
+        return (self.config.hidden_size, 3, ps, ps) if p["name"] == self.PATCH_KEY else super()._source_shape(p)
 
     @staticmethod
     def _canonical(sd: dict) -> dict:
         return {(k[len("vision_model."):] if k.startswith("vision_model.") else k): v for k, v in sd.items()}
 
-    def _pack_one(self, p: dict, t: torch.Tensor, device="cpu") -> torch.Tensor:
-        """One state_dict tensor in the engine layout, as raw bytes: vectors f32, matrices in the storage type; the patch weight
-        flattened in (c, ky, kx) order and zero-padded to the GEMM's k-tile."""
-        t = t.detach().to(device)
-        if p["cols"] == 0:
-            return t.to(torch.float32).reshape(-1).contiguous().view(torch.uint8)
+    def _pack_one(self, p: dict, t: torch.Tensor) -> torch.Tensor:
+        """The patch weight flattened in (c, ky, kx) order and zero-padded to the GEMM's k-tile."""
+        if tuple(t.shape) != self._source_shape(p):
+            raise _lib.SdnError(f"{p['name']}: expected shape {self._source_shape(p)}, got {tuple(t.shape)}")
         if p["name"] == self.PATCH_KEY:
-            flat = t.to(self.dtype).reshape(p["rows"], -1)
-            t = torch.zeros((p["rows"], p["cols"]), dtype=self.dtype, device=device)
-            t[:, :flat.shape[1]] = flat
-        return t.to(self.dtype).reshape(-1).contiguous().view(torch.uint8)
-
-    def _pack(self, sd: dict, device) -> torch.Tensor:
-        sd = self._canonical(sd)
-        missing = [p["name"] for p in self.manifest if p["name"] not in sd]
-        if missing:
-            raise KeyError(f"state_dict lacks {len(missing)} keys, e.g. {missing[:3]}")
-        shapes = self.state_dict_shapes()
-        buf = torch.zeros(self.weight_bytes, dtype=torch.uint8, device=device)
-        for p in self.manifest:
-            t = sd[p["name"]]
-            if tuple(t.shape) != shapes[p["name"]]:
-                raise _lib.SdnError(f"{p['name']}: expected shape {shapes[p['name']]}, got {tuple(t.shape)}")
-            raw = self._pack_one(p, t, device)
-            buf[p["offset"]:p["offset"] + raw.numel()].copy_(raw)
-        return buf
-
-    def pack_state_dict(self, sd: dict) -> torch.Tensor:
-        return self._pack(sd, "cpu")
-
-    def load_state_dict(self, sd: dict, device="cuda"):
-        _lib.require_gpu()
-        self._weights = self._pack(sd, device)                      # tensor by tensor into the device buffer
-        return self._prepare()
+            t = torch.nn.functional.pad(t.detach().reshape(p["rows"], -1), (0, p["cols"] - 3 * self.config.patch_size ** 2))
+        return super()._pack_one(p, t)
 
     @classmethod
     def from_pretrained(cls, local_dir: str, dtype=torch.float16, device="cuda"):

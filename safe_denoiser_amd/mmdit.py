@@ -1,24 +1,22 @@
 """SD3Transformer2DModel (MMDiT) front-end: the call surface the reference's SD-v3 pipelines use
 (`self.transformer(hidden_states=, timestep=, encoder_hidden_states=, pooled_projections=, return_dict=False)[0]`,
 models/sdv3/safe_denoiser_pipeline.py:1120-1127), executed by libsdn's static launch plan (sdn_mmdit_forward).
-Weights are addressed by their diffusers state_dict keys and packed once into the engine layout, exactly as for the UNet.
+Weights are addressed by their diffusers state_dict keys and packed once into the engine layout by EngineModel's packer (_model.py).
 """
 from __future__ import annotations
 
-import ctypes as C
 from types import SimpleNamespace
 
 import torch
 
 from . import _lib
-from .unet import P_CONV3X3, P_GEGLU_MAT, P_GEGLU_VEC, P_MAT, P_VEC_F32, UNet2DConditionModel
+from ._model import ALL_DTYPES, P_POS_CROP, EngineModel  # noqa: F401
 
-P_POS_CROP = 5
 SD3_MEDIUM = dict(in_channels=16, out_channels=16, sample_size=64, patch_size=2, num_layers=24, num_attention_heads=24,
                   attention_head_dim=64, joint_attention_dim=4096, pooled_projection_dim=2048, pos_embed_max_size=192)
 
 
-class SD3Transformer2DModel(UNet2DConditionModel):
+class SD3Transformer2DModel(EngineModel):
     """`sample_size` is the LATENT side this plan is built for (64 -> 512x512 images, the reference driver's default,
     run_nudity_sdv3.py:357-358,500; 128 -> 1024x1024).
     dtype=torch.float32 selects the fp32 precision plan (sdn_mmdit_config.dtype 2): weights, text, pooled projections and
@@ -27,14 +25,8 @@ class SD3Transformer2DModel(UNet2DConditionModel):
     Same meaning as UNet2DConditionModel's arguments."""
 
     def __init__(self, text_len: int = 333, dtype=torch.float16, precision: str | None = None, **config):
-        if precision not in (None, "fp32", "bf16x3"):
-            raise _lib.SdnError('precision must be None, "fp32" or "bf16x3"')
-        if precision is not None:
-            dtype = torch.float32                                   # both precision modes store f32
-        if dtype not in (torch.bfloat16, torch.float16, torch.float32):
-            raise _lib.SdnError("storage dtype must be torch.bfloat16, torch.float16 or torch.float32 (the precision mode)")
-        self.dtype = dtype
-        self.precision = precision or ("fp32" if dtype == torch.float32 else None)
+        code = self._storage(dtype, precision, ALL_DTYPES,
+                             "storage dtype must be torch.bfloat16, torch.float16 or torch.float32 (the precision mode)")
         cfg = dict(SD3_MEDIUM)
         cfg.update(config)
         self.config = SimpleNamespace(**cfg)
@@ -44,30 +36,21 @@ class SD3Transformer2DModel(UNet2DConditionModel):
                              sample_size=cfg["sample_size"], patch_size=cfg["patch_size"], num_layers=cfg["num_layers"],
                              num_heads=cfg["num_attention_heads"], head_dim=cfg["attention_head_dim"],
                              joint_dim=cfg["joint_attention_dim"], pooled_dim=cfg["pooled_projection_dim"],
-                             text_len=text_len, time_dim=256,
-                             dtype=3 if self.precision == "bf16x3" else {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}[dtype])
-        h = C.c_void_p()
-        _lib.check(_lib.lib().sdn_mmdit_create(C.byref(c), C.byref(h)), "sdn_mmdit_create")
-        self._h = h
-        self._weights = None
-        self._ws = {}
-        self._read_manifest()
+                             text_len=text_len, time_dim=256, dtype=code)
+        self._create("sdn_mmdit_create", c)
 
     # ---- parameters -------------------------------------------------------------------------------------
-    def state_dict_shapes(self) -> dict:
+    def _source_shape(self, p: dict) -> tuple:
         cfg = self.config
-        out = {}
-        for p in self.manifest:
-            k, r, c = p["kind"], p["rows"], p["cols"]
-            if k == P_VEC_F32:
-                out[p["name"]] = (r,)
-            elif k == P_POS_CROP:
-                out[p["name"]] = (1, cfg.pos_embed_max_size ** 2, c)
-            elif p["name"] == "pos_embed.proj.weight":
-                out[p["name"]] = (r, cfg.in_channels, cfg.patch_size, cfg.patch_size)
-            else:
-                out[p["name"]] = (r, c)
-        return out
+        if p["kind"] == P_POS_CROP:
+            return (1, cfg.pos_embed_max_size ** 2, p["cols"])
+        if p["name"] == "pos_embed.proj.weight":
+            return (p["rows"], cfg.in_channels, cfg.patch_size, cfg.patch_size)
+        return super()._source_shape(p)
+
+    @staticmethod
+    def _is_norm_param(name: str) -> bool:
+        return ".norm" in name                    # (the blocks' adaLN biases: their amplitude in load_synthetic_on_device)
 
     def synthetic_state_dict(self, seed: int = 1234) -> dict:
         g = torch.Generator().manual_seed(seed)
@@ -93,20 +76,8 @@ class SD3Transformer2DModel(UNet2DConditionModel):
         grid = pe.reshape(m, m, -1)
         return grid[top:top + hp, top:top + hp].reshape(hp * hp, -1)
 
-    def pack_state_dict(self, sd: dict) -> torch.Tensor:
-        """CPU uint8 buffer in the engine layout: matrices (and the cropped position embedding) in the plan's storage dtype -- f32 in
-        the precision plans, like every bias and modulation vector."""
-        buf = torch.zeros(self.weight_bytes, dtype=torch.uint8)
-        for p in self.manifest:
-            t = sd[p["name"]].detach().float().cpu()
-            k = p["kind"]
-            if k == P_POS_CROP:
-                t = self.crop_pos_embed(t)
-            elif k == P_MAT:
-                t = t.reshape(p["rows"], p["cols"])
-            raw = t.contiguous().view(torch.uint8) if k == P_VEC_F32 else t.to(self.dtype).contiguous().view(torch.uint8)
-            buf[p["offset"]:p["offset"] + raw.numel()] = raw.reshape(-1)
-        return buf
+    def _pack_one(self, p: dict, t: torch.Tensor) -> torch.Tensor:
+        return super()._pack_one(p, self.crop_pos_embed(t) if p["kind"] == P_POS_CROP else t)
 
     # ---- forward ------------------------------------------------------------------------------------------
     def prepare_text(self, encoder_hidden_states: torch.Tensor) -> torch.Tensor:

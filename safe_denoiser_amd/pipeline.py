@@ -414,8 +414,8 @@ class SafeDenoiserPipeline:
         # plans in this call, shared latents, and the engine's own UNet class on both sides
         from .unet import UNet2DConditionModel
         dead_lo = bool(self.dead_branch_lo and self.unet_hi is not None and nb == 3 and sf["lra"] and not sld and shared_latents
-                       and any(use_hi) and not all(use_hi) and type(self.unet) is UNet2DConditionModel
-                       and type(self.unet_hi) is UNet2DConditionModel)
+                       and any(use_hi) and not all(use_hi) and isinstance(self.unet, UNet2DConditionModel)
+                       and isinstance(self.unet_hi, UNet2DConditionModel))
         hi2 = lo1 = None
         n_dead_lo = 0
         if dead_lo:
@@ -553,14 +553,11 @@ class SafeDenoiserPipeline:
 
     def _sibling(self, net, rep: int):
         """A second launch plan over `net`'s packed weights with another latent_repeat (kept for the pipeline's lifetime)."""
-        from .unet import UNet2DConditionModel
         key = (id(net), rep)
         sib = self._sib.get(key)
         if sib is None:
-            sib = self._sib[key] = UNet2DConditionModel(text_len=net.text_len, dtype=net.dtype, latent_repeat=rep,
-                                                        precision=net.precision if net.precision in ("fp32", "bf16x3") else None,
-                                                        **vars(net.config))
-        sib._weights = net._weights                                   # the derived regions live in the buffer: nothing to prepare again
+            sib = self._sib[key] = net.sibling(rep)
+        sib._weights = net._weights                                   # reloaded weights are picked up at the next use
         return sib
 
     # ---- precision schedule ---------------------------------------------------------------------------------

@@ -3,7 +3,7 @@
 token), executed by libsdn's launch plan (sdn_t5_create / sdn_t5_forward).
 
 Weights: a transformers T5EncoderModel state_dict (keys with or without the `encoder.` prefix; `shared.weight` stands in for
-`embed_tokens.weight`), packed once into the engine layout.  The tokenizer stays with the caller: pass token ids.  The sequence
+`embed_tokens.weight`), packed once into the engine layout by EngineModel's packer (_model.py).  The tokenizer stays with the caller: pass token ids.  The sequence
 length is whatever the ids have (2 .. 512): the masked-token call pads to the prompt's own length.
 """
 from __future__ import annotations
@@ -14,9 +14,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
-from .unet import UNet2DConditionModel
-
-P_GLU_VALUE, P_GLU_GATE = 7, 8
+from ._model import HALF_DTYPES, P_GLU_GATE, P_GLU_VALUE, EngineModel
 
 # T5-v1.1-XXL as SD-v3 ships it (text_encoder_3/config.json)
 T5_XXL_CONFIG = dict(vocab_size=32128, d_model=4096, d_kv=64, d_ff=10240, num_layers=24, num_heads=64,
@@ -33,32 +31,21 @@ class T5EncoderOutput(tuple):
         return o
 
 
-class T5EncoderModel(UNet2DConditionModel):
+class T5EncoderModel(EngineModel):
     def __init__(self, dtype=torch.bfloat16, **config):
-        if dtype not in (torch.bfloat16, torch.float16):
-            raise _lib.SdnError("storage dtype must be torch.bfloat16 or torch.float16 (fp32-storage T5 modes are not built yet)")
-        self.dtype = dtype
-        self.precision = None
-        self.latent_repeat = 1
+        code = self._storage(dtype, None, HALF_DTYPES,
+                             "storage dtype must be torch.bfloat16 or torch.float16 (fp32-storage T5 modes are not built yet)")
         cfg = dict(T5_XXL_CONFIG)
         cfg.update(config)
         self.config = SimpleNamespace(**cfg)
         c = _lib.T5Config(vocab_size=cfg["vocab_size"], d_model=cfg["d_model"], d_kv=cfg["d_kv"], d_ff=cfg["d_ff"],
                           num_layers=cfg["num_layers"], num_heads=cfg["num_heads"],
                           num_buckets=cfg["relative_attention_num_buckets"], max_distance=cfg["relative_attention_max_distance"],
-                          eps=cfg["layer_norm_epsilon"], dtype={torch.bfloat16: 0, torch.float16: 1}[dtype])
-        h = C.c_void_p()
-        _lib.check(_lib.lib().sdn_t5_create(C.byref(c), C.byref(h)), "sdn_t5_create")
-        self._h = h
-        self._weights = None
-        self._ws = {}
-        self._read_manifest()
+                          eps=cfg["layer_norm_epsilon"], dtype=code)
+        self._create("sdn_t5_create", c)
         # rows of one launch: the GEMM tiles address an operand with 31-bit byte offsets
         widest = max(cfg["d_ff"], 3 * cfg["num_heads"] * cfg["d_kv"], 2 * cfg["d_model"])
         self.max_rows = ((1 << 31) - 4096) // (2 * widest)
-
-    def state_dict_shapes(self) -> dict:
-        return {p["name"]: ((p["rows"],) if p["cols"] == 0 else (p["rows"], p["cols"])) for p in self.manifest}
 
     @staticmethod
     def _is_norm_param(name: str) -> bool:
@@ -78,48 +65,11 @@ class T5EncoderModel(UNet2DConditionModel):
         pair = buf[base:base + 2 * f * k * es].view(self.dtype).view(f // 16, 2, 16, k)
         return pair[:, 1 if p["kind"] == P_GLU_GATE else 0]
 
-    def _fill(self, buf: torch.Tensor, sd: dict):
-        for p in self.manifest:
-            t = sd[p["name"]]
-            if p["kind"] in (P_GLU_VALUE, P_GLU_GATE):
-                self._glu_view(buf, p).copy_(t.detach().to(self.dtype).reshape(p["rows"] // 16, 16, p["cols"]))
-            else:                                         # (converted where the tensor lives: device-resident state dicts stay there)
-                t = t.detach().to(torch.float32 if p["cols"] == 0 else self.dtype).reshape(-1).contiguous()
-                raw = t.view(torch.uint8)
-                buf[p["offset"]:p["offset"] + raw.numel()].copy_(raw)
-        return buf
-
-    def pack_state_dict(self, sd: dict) -> torch.Tensor:
-        return self._fill(torch.zeros(self.weight_bytes, dtype=torch.uint8), self._canonical(sd))
-
-    def load_state_dict(self, sd: dict, device="cuda"):
-        sd = self._canonical(sd)
-        missing = [p["name"] for p in self.manifest if p["name"] not in sd]
-        if missing:
-            raise KeyError(f"state_dict lacks {len(missing)} keys, e.g. {missing[:3]}")
-        _lib.require_gpu()
-        # tensor by tensor into the device buffer: the 9.5 GB of T5-XXL never exist twice on the host
-        self._weights = self._fill(torch.zeros(self.weight_bytes, dtype=torch.uint8, device=device), sd)
-        return self._prepare()
-
-    def load_synthetic_on_device(self, seed: int = 1234, device="cuda"):
-        """Random weights of synthetic_state_dict()'s distributions, generated in the packed layout on the GPU."""
-        _lib.require_gpu()
-        g = torch.Generator(device=device).manual_seed(seed)
-        buf = torch.zeros(self.weight_bytes, dtype=torch.uint8, device=device)
-        for p in self.manifest:
-            n = p["rows"] * max(p["cols"], 1)
-            if p["cols"] == 0:
-                t = 1.0 + (torch.rand(n, generator=g, device=device) - 0.5) * 0.1
-                buf[p["offset"]:p["offset"] + 4 * n] = t.view(torch.uint8)
-                continue
-            t = ((torch.rand(n, generator=g, device=device) * 2 - 1) * (3.0 / p["cols"]) ** 0.5).to(self.dtype)
-            if p["kind"] in (P_GLU_VALUE, P_GLU_GATE):
-                self._glu_view(buf, p).copy_(t.view(p["rows"] // 16, 16, p["cols"]))
-            else:
-                buf[p["offset"]:p["offset"] + t.element_size() * n] = t.view(torch.uint8)
-        self._weights = buf
-        return self._prepare()
+    def _store(self, buf: torch.Tensor, p: dict, t: torch.Tensor):
+        if p["kind"] in (P_GLU_VALUE, P_GLU_GATE):
+            self._glu_view(buf, p).copy_(t.view(p["rows"] // 16, 16, p["cols"]))
+        else:
+            super()._store(buf, p, t)
 
     def flops(self, batch: int, n: int = 256):
         a = C.c_double()

@@ -6,6 +6,8 @@ Weights: a diffusers-keyed state_dict (the names of `UNet2DConditionModel.state_
 ONCE into a single device buffer in the engine's layouts, driven by the manifest the C side publishes
 (sdn_unet_param_info): conv kernels [O,I,3,3] -> [O][ky][kx][I] bf16, linears / 1x1 convs -> [O][I] bf16,
 GEGLU projection rows interleaved value/gate in blocks of 16, norms and biases f32.
+The handle, the manifest and the packer are EngineModel's (_model.py), shared with every other front-end; this file adds the
+GEGLU layout and what only a UNet has: latent_repeat, the text K / V cache, tail split and chunking, graph mode, split-K.
 dtype=torch.float32 selects the plan's PRECISION mode (sdn_unet_config.dtype 2): weights, text and activations stay f32 and
 the contractions run on the f32-input matrix cores -- 1/16 of the 16-bit rate, ~1e-6 per forward from the fp32 reference.
 """
@@ -18,15 +20,12 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
+from ._model import ALL_DTYPES, P_CONV3X3, P_DERIVED, P_GEGLU_MAT, P_GEGLU_VEC, P_MAT, P_VEC_F32, EngineModel  # noqa: F401
 
 SD14_CONFIG = dict(in_channels=4, out_channels=4, sample_size=64, block_out_channels=(320, 640, 1280, 1280),
                    down_block_types=("CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "CrossAttnDownBlock2D",
                                      "DownBlock2D"),
                    layers_per_block=2, attention_head_dim=8, cross_attention_dim=768, norm_num_groups=32)
-
-P_VEC_F32, P_MAT, P_CONV3X3, P_GEGLU_MAT, P_GEGLU_VEC = 0, 1, 2, 3, 4
-P_DERIVED = 6      # regions the engine fills itself (sdn_unet_prepare): not state_dict tensors
-
 
 class UNetOutput:
     __slots__ = ("sample",)
@@ -43,7 +42,7 @@ def _interleave16(t: torch.Tensor) -> torch.Tensor:
     return torch.stack([v.reshape(f // 16, 16, *rest), g.reshape(f // 16, 16, *rest)], dim=1).reshape(2 * f, *rest)
 
 
-class UNet2DConditionModel:
+class UNet2DConditionModel(EngineModel):
     def __init__(self, text_len: int = 77, dtype=torch.bfloat16, latent_repeat: int = 1, precision: str | None = None, **config):
         """precision = "bf16x3" (with dtype=torch.float32, or alone): fp32 storage with split-operand contractions on the bf16
         matrix cores (sdn_unet_config.dtype 3, sdn_gemm_x3) -- the mode that meets the north star's 1e-3 at a multiple of the
@@ -51,14 +50,8 @@ class UNet2DConditionModel:
         latent_repeat = r > 1: the engine-side form of `torch.cat([latents] * r)` (classifier-free guidance): `sample`
         then holds B / r latents, `encoder_hidden_states` stays [B] branch-major, and everything up to the first
         cross-attention is computed once per latent (sdn_unet_config.latent_repeat).  Bit-identical results."""
-        if precision not in (None, "fp32", "bf16x3"):
-            raise _lib.SdnError('precision must be None, "fp32" or "bf16x3"')
-        if precision is not None:
-            dtype = torch.float32                                   # both precision modes store f32
-        if dtype not in (torch.bfloat16, torch.float16, torch.float32):
-            raise _lib.SdnError("storage dtype must be torch.bfloat16, torch.float16 or torch.float32 (the precision mode)")
-        self.dtype = dtype
-        self.precision = precision or ("fp32" if dtype == torch.float32 else None)
+        code = self._storage(dtype, precision, ALL_DTYPES,
+                             "storage dtype must be torch.bfloat16, torch.float16 or torch.float32 (the precision mode)")
         self.latent_repeat = max(1, int(latent_repeat))
         cfg = dict(SD14_CONFIG)
         cfg.update(config)
@@ -75,151 +68,34 @@ class UNet2DConditionModel:
                             layers_per_block=cfg["layers_per_block"], n_heads=cfg["attention_head_dim"],
                             cross_dim=cfg["cross_attention_dim"], text_len=text_len,
                             norm_groups=cfg["norm_num_groups"],
-                            dtype=3 if self.precision == "bf16x3" else {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}[dtype],
-                            latent_repeat=self.latent_repeat)
-        h = C.c_void_p()
-        _lib.check(_lib.lib().sdn_unet_create(C.byref(c), C.byref(h)), "sdn_unet_create")
-        self._h = h
-        self._weights = None
-        self._ws = {}
+                            dtype=code, latent_repeat=self.latent_repeat)
         self.tail_split = False            # set_tail_split(): see _tail_split_of
-        self._read_manifest()
-
-    def _read_manifest(self):
-        """diffusers-keyed tensors -> self.manifest; engine-derived regions (SDN_P_DERIVED) are left to _prepare()."""
-        h = self._h
-        self.manifest = []
-        info = _lib.ParamInfo()
-        for i in range(_lib.lib().sdn_unet_param_count(h)):
-            _lib.check(_lib.lib().sdn_unet_param_info(h, i, C.byref(info)), "sdn_unet_param_info")
-            if info.kind == P_DERIVED:
-                continue
-            self.manifest.append(dict(name=info.name.decode(), kind=info.kind, rows=info.rows, cols=info.cols,
-                                      rows_padded=info.rows_padded, offset=info.offset))
-        self.weight_bytes = _lib.lib().sdn_unet_weight_bytes(h)
-
-    def _prepare(self):
-        """Let the engine fill its derived weight regions (LayerNorm-folded projections) from the uploaded tensors."""
-        _lib.check(_lib.lib().sdn_unet_prepare(self._h, _lib.dptr(self._weights), _lib.stream_ptr()), "sdn_unet_prepare")
-        return self
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _lib.lib().sdn_unet_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        self._create("sdn_unet_create", c)
 
     # ---- parameters ---------------------------------------------------------------------------------
-    def state_dict_shapes(self) -> dict:
-        """diffusers key -> source tensor shape."""
-        out = {}
-        cin = self.config.in_channels
-        for p in self.manifest:
-            k, r, c = p["kind"], p["rows"], p["cols"]
-            if k in (P_VEC_F32, P_GEGLU_VEC):
-                out[p["name"]] = (r,)
-            elif k == P_CONV3X3:
-                out[p["name"]] = (r, c // 9, 3, 3)
-            elif p["name"].endswith(("proj_in.weight", "proj_out.weight", "conv_shortcut.weight")):
-                out[p["name"]] = (r, c, 1, 1)
-            else:
-                out[p["name"]] = (r, c)
-        del cin
-        return out
+    def _source_shape(self, p: dict) -> tuple:
+        if p["name"].endswith(("proj_in.weight", "proj_out.weight", "conv_shortcut.weight")):
+            return (p["rows"], p["cols"], 1, 1)
+        return super()._source_shape(p)
 
     @staticmethod
     def _is_norm_param(name: str) -> bool:
         return ".norm" in name or name.startswith("conv_norm_out")
 
-    def synthetic_state_dict(self, seed: int = 1234) -> dict:
-        """Random weights of this architecture (there are no checkpoints on the box): variance-preserving
-        uniform U(-sqrt(3/fan_in), sqrt(3/fan_in)) for matrices, small uniform biases, norm gains near 1."""
-        g = torch.Generator().manual_seed(seed)
-        sd = {}
-        for name, shape in self.state_dict_shapes().items():
-            if len(shape) == 1:
-                if self._is_norm_param(name):
-                    base = 1.0 if name.endswith("weight") else 0.0
-                    sd[name] = base + 0.1 * (torch.rand(shape, generator=g) - 0.5)
-                else:
-                    sd[name] = 0.2 * (torch.rand(shape, generator=g) - 0.5)
-            else:
-                fan_in = 1
-                for d in shape[1:]:
-                    fan_in *= d
-                bound = (3.0 / fan_in) ** 0.5
-                sd[name] = (torch.rand(shape, generator=g) * 2 - 1) * bound
-        return sd
-
     def _pack_one(self, p: dict, t: torch.Tensor) -> torch.Tensor:
-        """One state_dict tensor in the engine layout, as raw bytes (uint8, 1-D)."""
-        t = t.detach().float().cpu()
-        k = p["kind"]
-        if k == P_CONV3X3:
-            t = t.permute(0, 2, 3, 1).reshape(p["rows"], p["cols"])
-        elif k in (P_MAT, P_GEGLU_MAT):
-            t = t.reshape(p["rows"], p["cols"])
-        if k in (P_GEGLU_MAT, P_GEGLU_VEC):
-            t = _interleave16(t)
-        if k not in (P_VEC_F32, P_GEGLU_VEC):
-            t = t.to(self.dtype)
-        return t.contiguous().view(torch.uint8).reshape(-1)
+        """GEGLU projections: value / gate rows interleaved in blocks of 16."""
+        t = super()._pack_one(p, t)
+        return _interleave16(t) if p["kind"] in (P_GEGLU_MAT, P_GEGLU_VEC) else t
 
-    def pack_state_dict(self, sd: dict) -> torch.Tensor:
-        """CPU uint8 buffer in the engine layout."""
-        buf = torch.zeros(self.weight_bytes, dtype=torch.uint8)
-        for p in self.manifest:
-            raw = self._pack_one(p, sd[p["name"]])
-            buf[p["offset"]:p["offset"] + raw.numel()] = raw
-        return buf
-
-    def load_state_dict(self, sd: dict, device="cuda"):
-        missing = [p["name"] for p in self.manifest if p["name"] not in sd]
-        if missing:
-            raise KeyError(f"state_dict lacks {len(missing)} keys, e.g. {missing[:3]}")
-        _lib.require_gpu()
-        if type(self).pack_state_dict is not UNet2DConditionModel.pack_state_dict:
-            # a subclass with its own packing rules (MMDiT position-embedding crop, VAE 1x1 mixers, CLIP key prefixes)
-            self._weights = self.pack_state_dict(sd).to(device)
-            return self._prepare()
-        # tensor by tensor into the device buffer: the engine-derived regions between them (LayerNorm-folded / product weights;
-        # in the bf16x3 plan the expanded bf16 copy of every matrix, 1.5 x the f32 weights) never exist on the host
-        buf = torch.zeros(self.weight_bytes, dtype=torch.uint8, device=device)
-        for p in self.manifest:
-            raw = self._pack_one(p, sd[p["name"]])
-            buf[p["offset"]:p["offset"] + raw.numel()].copy_(raw)
-        self._weights = buf
-        return self._prepare()
-
-    def load_synthetic_on_device(self, seed: int = 1234, device="cuda"):
-        """Random weights generated DIRECTLY in the packed engine layout on the GPU (benchmarks: no checkpoints exist
-        on the box and the 0.86 G-parameter CPU generate+pack path takes tens of seconds per rank).  Same distributions
-        as synthetic_state_dict(); the values are not the CPU generator's, so parity tests use the state_dict path."""
-        _lib.require_gpu()
-        g = torch.Generator(device=device).manual_seed(seed)
-        buf = torch.zeros(self.weight_bytes, dtype=torch.uint8, device=device)
-        for p in self.manifest:
-            n = p["rows"] * max(p["cols"], 1)
-            if p["kind"] in (P_VEC_F32, P_GEGLU_VEC):
-                is_gain = self._is_norm_param(p["name"]) and p["name"].endswith("weight")
-                is_nb = self._is_norm_param(p["name"]) and p["name"].endswith("bias")
-                amp = 0.1 if (is_gain or is_nb) else 0.2
-                t = (torch.rand(n, generator=g, device=device) - 0.5) * amp + (1.0 if is_gain else 0.0)
-                buf[p["offset"]:p["offset"] + 4 * n] = t.view(torch.uint8)
-            else:
-                t = ((torch.rand(n, generator=g, device=device) * 2 - 1) * (3.0 / max(p["cols"], 1)) ** 0.5).to(self.dtype)
-                buf[p["offset"]:p["offset"] + t.element_size() * n] = t.view(torch.uint8)
-        self._weights = buf
-        return self._prepare()
+    def sibling(self, latent_repeat: int | None = None):
+        """A second handle over the SAME packed weights (its own launch plans, workspace and text K / V cache), with this one's
+        latent_repeat or another.  The derived regions live in the weight buffer: nothing to prepare again."""
+        net = UNet2DConditionModel(text_len=self.text_len, dtype=self.dtype, precision=self.precision,
+                                   latent_repeat=self.latent_repeat if latent_repeat is None else latent_repeat, **vars(self.config))
+        net._weights = self._weights
+        return net
 
     # ---- forward --------------------------------------------------------------------------------------
-    def flops(self, batch: int):
-        a = C.c_double()
-        total = _lib.lib().sdn_unet_flops(self._h, batch, C.byref(a))
-        return total, a.value
-
     def set_graph_mode(self, on: bool = True):
         """Replay each forward as one hipGraph (sdn_unet_set_graph_mode): worth it when the batch is small enough for the
         ~850 launches of a forward to be the bound (a single prompt: 13 ms -> a few ms per step).  Identical results."""
@@ -239,26 +115,6 @@ class UNet2DConditionModel:
         _lib.lib().sdn_unet_set_split_k(self._h, 1 if on else 0)
         self._ws = {}
         return self
-
-    def profile_next(self):
-        """Arm HIP-event profiling of the next forward (diagnostics; see sdn_unet_profile_next)."""
-        _lib.lib().sdn_unet_profile_next(self._h)
-
-    def profile_read(self) -> list:
-        rows = (_lib.ProfileRow * 32)()
-        n = _lib.lib().sdn_unet_profile_read(self._h, rows, 32)
-        if n < 0:
-            raise _lib.SdnError("sdn_unet_profile_read failed (no profiled forward?)")
-        return [dict(kernel=rows[i].kernel.decode(), launches=rows[i].launches, ms=rows[i].ms, flops=rows[i].flops,
-                     bytes=rows[i].bytes) for i in range(n)]
-
-    def _workspace(self, batch: int, device):
-        ws = self._ws.get(batch)
-        if ws is None:
-            n = _lib.lib().sdn_unet_workspace_bytes(self._h, batch)
-            ws = torch.empty(n, dtype=torch.uint8, device=device)
-            self._ws[batch] = ws
-        return ws
 
     def prepare_text(self, encoder_hidden_states: torch.Tensor) -> torch.Tensor:
         e = encoder_hidden_states
@@ -284,7 +140,7 @@ class UNet2DConditionModel:
     def _tail_split_of(self, b: int):
         """(latents in the aligned main forward, latents in the tail), or None when the batch runs as one forward."""
         rep = self.latent_repeat
-        if not getattr(self, "tail_split", False) or rep <= 1 or type(self) is not UNet2DConditionModel:
+        if not self.tail_split or rep <= 1:
             return None
         p = b // rep
         q = 64 // math.gcd(64, rep)                                  # latents per 64-sample quantum
@@ -314,8 +170,6 @@ class UNet2DConditionModel:
         cut: the tail rule above, and a batch above `max_samples()` (it used to fail with SDN_E_INVALID): whole-wave chunks (multiples of
         64 samples) one after the other on the caller's stream, each on its own handle (its own workspace and text K / V cache), a
         small remainder beside them."""
-        if type(self) is not UNet2DConditionModel:
-            return None
         rep = self.latent_repeat
         p = b // rep
         cap = self.max_samples() // rep                                # latents one plan takes
@@ -326,7 +180,7 @@ class UNet2DConditionModel:
         per = cap // q * q if cap >= q else cap                        # whole waves of tiles where the cap allows it
         chunks = [(lo, min(per, p - lo), False) for lo in range(0, p, per)]
         lo, n, _ = chunks[-1]
-        if n * rep <= self.TAIL_MAX_SAMPLES and getattr(self, "tail_split", False) and rep > 1:
+        if n * rep <= self.TAIL_MAX_SAMPLES and self.tail_split and rep > 1:
             chunks[-1] = (lo, n, True)
         return chunks
 
@@ -335,10 +189,8 @@ class UNet2DConditionModel:
         p = sample.shape[0]
         st = getattr(self, "_split", None)
         if st is None or st["key"] != (p, tuple(chunks), dev):
-            kw = dict(text_len=self.text_len, dtype=self.dtype, latent_repeat=rep,
-                      precision=self.precision if self.precision in ("fp32", "bf16x3") else None, **vars(self.config))
             tshape, oshape = tuple(text.shape[1:]), tuple(out.shape[1:])
-            parts = [dict(lo=lo, n=n, side=side, net=self if i == 0 else UNet2DConditionModel(**kw),
+            parts = [dict(lo=lo, n=n, side=side, net=self if i == 0 else self.sibling(),
                           # rep = 1: a chunk's text / output rows are contiguous views of the caller's tensors, nothing is staged
                           text=None if rep == 1 else torch.empty((rep * n,) + tshape, dtype=self.dtype, device=dev),
                           out=None if rep == 1 else torch.empty((rep * n,) + oshape, dtype=torch.float32, device=dev))
@@ -395,7 +247,7 @@ class UNet2DConditionModel:
 
     def _forward_one(self, sample, timestep, text_bf16, out):
         b = text_bf16.shape[0]
-        if type(self) is UNet2DConditionModel and b > self.max_samples():
+        if b > self.max_samples():
             raise _lib.SdnError(f"{b} samples exceed what one launch plan addresses ({self.max_samples()}): forward_into cuts such batches")
         ws = self._workspace(b, sample.device)
         _lib.check(_lib.lib().sdn_unet_forward(self._h, _lib.dptr(self._weights), _lib.dptr(sample, torch.float32),

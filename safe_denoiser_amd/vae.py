@@ -8,7 +8,7 @@ The encoder half serves the proj_ref builder's embed_fn, `vae.encode(x).latent_d
 sdn_vae_encode / sdn_gaussian_sample.
 
 Weights: the `post_quant_conv.*` + `decoder.*` (and, when present, `quant_conv.*` + `encoder.*`) entries of a diffusers
-AutoencoderKL state_dict (SD-v1.4 `vae/`), packed once into the engine layout exactly like the UNet's.  The deprecated attention names of the on-disk checkpoint
+AutoencoderKL state_dict (SD-v1.4 `vae/`), packed once into the engine layout by EngineModel's packer (_model.py).  The deprecated attention names of the on-disk checkpoint
 (`query/key/value/proj_attn`) are accepted as aliases of `to_q/to_k/to_v/to_out.0`.
 """
 from __future__ import annotations
@@ -19,7 +19,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
-from .unet import UNet2DConditionModel
+from ._model import HALF_DTYPES, EngineModel
 
 SD14_VAE_CONFIG = dict(in_channels=3, out_channels=3, latent_channels=4, block_out_channels=(128, 256, 512, 512),
                        layers_per_block=2, norm_num_groups=32, sample_size=512, scaling_factor=0.18215, shift_factor=0.0,
@@ -77,7 +77,7 @@ class EncoderOutput:
         self.latent_dist = latent_dist
 
 
-class AutoencoderKL(UNet2DConditionModel):
+class AutoencoderKL(EngineModel):
     """AutoencoderKL.  `sample_size` is the IMAGE side (diffusers' meaning); the latent side is
     sample_size / 2**(levels-1).  The object itself is the decoder half; `.encoder_half` (built on first use or when
     the state_dict carries `encoder.*`) is the same class in the encoder role."""
@@ -85,9 +85,7 @@ class AutoencoderKL(UNet2DConditionModel):
     MAX_CHUNK = 8                      # images per plan invocation; sdn_vae_* chunk larger batches themselves (32-bit DMA offsets)
 
     def __init__(self, dtype=torch.bfloat16, _role: str = "decoder", **config):
-        if dtype not in (torch.bfloat16, torch.float16):
-            raise _lib.SdnError("storage dtype must be torch.bfloat16 or torch.float16")
-        self.dtype = dtype
+        code = self._storage(dtype, None, HALF_DTYPES, "storage dtype must be torch.bfloat16 or torch.float16")
         cfg = dict(SD14_VAE_CONFIG)
         cfg.update(config)
         self.config = SimpleNamespace(**cfg)
@@ -103,33 +101,20 @@ class AutoencoderKL(UNet2DConditionModel):
                            sample_size=self.latent_size, n_levels=n,
                            block_out_channels=(C.c_int32 * 4)(*(boc + [0] * (4 - n))),
                            layers_per_block=cfg["layers_per_block"], norm_groups=cfg["norm_num_groups"],
-                           dtype=0 if dtype == torch.bfloat16 else 1)
-        h = C.c_void_p()
+                           dtype=code)
         self._role = _role
         self._user_config = dict(config)
         self.encoder_half = None
-        if _role == "encoder":
-            _lib.check(_lib.lib().sdn_vae_encoder_create(C.byref(c), C.byref(h)), "sdn_vae_encoder_create")
-        else:
-            _lib.check(_lib.lib().sdn_vae_decoder_create(C.byref(c), C.byref(h)), "sdn_vae_decoder_create")
-        self._h = h
-        self._weights = None
-        self._ws = {}
-        self._read_manifest()
+        self._create("sdn_vae_encoder_create" if _role == "encoder" else "sdn_vae_decoder_create", c)
 
     # ---- parameters ---------------------------------------------------------------------------------
-    @staticmethod
-    def _is_norm_param(name: str) -> bool:
-        return "norm" in name.split(".")[-2]
-
-    def state_dict_shapes(self) -> dict:
-        out = super().state_dict_shapes()
+    def _source_shape(self, p: dict) -> tuple:
         L = self.config.latent_channels
-        if self._role == "encoder":
-            out["quant_conv.weight"] = (2 * L, 2 * L, 1, 1)
-        else:
-            out["post_quant_conv.weight"] = (L, L, 1, 1)
-        return out
+        if p["name"] in ("quant_conv.weight", "post_quant_conv.weight"):         # (the plan keeps the 1x1 mixer as an f32 vector)
+            return (2 * L, 2 * L, 1, 1) if self._role == "encoder" else (L, L, 1, 1)
+        if p["name"].endswith(("proj_in.weight", "proj_out.weight", "conv_shortcut.weight")):
+            return (p["rows"], p["cols"], 1, 1)
+        return super()._source_shape(p)
 
     def _encoder(self):
         if self.encoder_half is None:
@@ -148,29 +133,15 @@ class AutoencoderKL(UNet2DConditionModel):
             out[k] = v
         return out
 
-    def pack_state_dict(self, sd: dict) -> torch.Tensor:
-        sd = self._canonical(sd)
-        sd = dict(sd)
+    def _pack(self, sd: dict, device) -> torch.Tensor:
         # VAEs without (post_)quant_conv (SD-v3): the plan's 1x1 mixing stage gets the identity
-        L = self.config.latent_channels
-        if self._role == "decoder" and not self.config.use_post_quant_conv:
-            sd["post_quant_conv.weight"], sd["post_quant_conv.bias"] = torch.eye(L).reshape(L, L, 1, 1), torch.zeros(L)
-        if self._role == "encoder" and not self.config.use_quant_conv:
-            sd["quant_conv.weight"], sd["quant_conv.bias"] = torch.eye(2 * L).reshape(2 * L, 2 * L, 1, 1), torch.zeros(2 * L)
-        qk = "quant_conv.weight" if self._role == "encoder" else "post_quant_conv.weight"
-        sd[qk] = sd[qk].reshape(-1)                                                   # [C, C, 1, 1] -> fp32 vector
-        for k in list(sd):                                                            # deprecated linears stored as 1x1 convs
-            if "attentions" in k and k.endswith("weight") and sd[k].dim() == 4:
-                sd[k] = sd[k].reshape(sd[k].shape[0], sd[k].shape[1])
-        return super().pack_state_dict(sd)
+        n = self.config.latent_channels * (2 if self._role == "encoder" else 1)
+        if not (self.config.use_quant_conv if self._role == "encoder" else self.config.use_post_quant_conv):
+            q = "quant_conv" if self._role == "encoder" else "post_quant_conv"
+            sd = {**sd, q + ".weight": torch.eye(n).reshape(n, n, 1, 1), q + ".bias": torch.zeros(n)}
+        return super()._pack(sd, device)
 
     def load_state_dict(self, sd: dict, device="cuda"):
-        sd = dict(self._canonical(sd))
-        L = self.config.latent_channels
-        if self._role == "decoder" and not self.config.use_post_quant_conv:
-            sd.setdefault("post_quant_conv.weight", torch.eye(L).reshape(L, L, 1, 1)); sd.setdefault("post_quant_conv.bias", torch.zeros(L))
-        if self._role == "encoder" and not self.config.use_quant_conv:
-            sd.setdefault("quant_conv.weight", torch.eye(2 * L).reshape(2 * L, 2 * L, 1, 1)); sd.setdefault("quant_conv.bias", torch.zeros(2 * L))
         if self._role == "decoder" and "encoder.conv_in.weight" in sd:
             self._encoder().load_state_dict(sd, device)
         return super().load_state_dict(sd, device)

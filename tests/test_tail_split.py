@@ -1,11 +1,19 @@
 """The host rule that decides when a UNet forward runs as an aligned part + a concurrent tail (unet._tail_split_of; the GPU tests
 `test_tail_split_forward_is_the_single_forward` / `test_a_batch_a_few_prompts_over_whole_waves_...` hold the bits).  No GPU here."""
+import pytest
+
+from safe_denoiser_amd.clip import CLIPTextModel, CLIPTextModelWithProjection
+from safe_denoiser_amd.clip_vision import CLIPVisionModelWithProjection
 from safe_denoiser_amd.mmdit import SD3Transformer2DModel
+from safe_denoiser_amd.t5 import T5EncoderModel
 from safe_denoiser_amd.unet import UNet2DConditionModel
+from safe_denoiser_amd.vae import AutoencoderKL
+
+UNET_ONLY = ("_tail_split_of", "_chunks_of", "set_tail_split")
 
 
-def _net(rep, on=True, cls=UNet2DConditionModel):
-    u = object.__new__(cls)                      # the rule reads three attributes; no engine handle needed
+def _net(rep, on=True):
+    u = object.__new__(UNet2DConditionModel)     # the rule reads two attributes; no engine handle needed
     u.latent_repeat, u.tail_split = rep, on
     return u
 
@@ -28,7 +36,7 @@ def test_rule_splits_only_a_small_tail_over_a_multiple_of_64_samples():
 def test_rule_is_off_by_default_without_shared_latents_and_for_the_other_plans():
     assert _net(3, on=False)._tail_split_of(195) is None
     assert _net(1)._tail_split_of(65) is None                       # branch-major rows cannot be cut per prompt without the repeat count
-    assert _net(3, cls=SD3Transformer2DModel)._tail_split_of(195) is None
+    assert not hasattr(SD3Transformer2DModel, "_tail_split_of")     # the other plans have no such rule at all
     for pm_r in (_net(3)._tail_split_of(3 * p) for p in range(1, 400)):
         if pm_r is not None:
             pm, r = pm_r
@@ -66,7 +74,15 @@ def test_batches_above_the_plan_limit_are_cut_into_whole_wave_chunks():
     assert plain._chunks_of(273) is None and plain._chunks_of(384) == [(0, 256, False), (256, 128, False)]
     two = UNet2DConditionModel(text_len=77, latent_repeat=2)
     assert two._chunks_of(2 * 136) is None and two._chunks_of(2 * 137) == [(0, 128, False), (128, 9, False)]
-    assert _net(3, cls=SD3Transformer2DModel)._chunks_of(3000) is None                         # other plans keep their own rules
+    assert not hasattr(SD3Transformer2DModel, "_chunks_of") and not hasattr(SD3Transformer2DModel, "set_tail_split")   # other plans keep their own rules
     x3 = UNet2DConditionModel(text_len=77, latent_repeat=3, precision="bf16x3")               # fp32 storage: 3/4 of the 16-bit limit
     assert x3.max_samples() == 204 and x3._chunks_of(3 * 68) is None and x3._chunks_of(3 * 70) == [(0, 64, False), (64, 6, False)]
     assert SD3Transformer2DModel(sample_size=64).max_samples() == 170 and SD3Transformer2DModel(sample_size=128).max_samples() == 42
+
+
+@pytest.mark.parametrize("cls", [SD3Transformer2DModel, AutoencoderKL, CLIPTextModel, CLIPTextModelWithProjection, T5EncoderModel,
+                                 CLIPVisionModelWithProjection])
+def test_no_other_front_end_is_a_unet_or_has_its_rules(cls):
+    assert not issubclass(cls, UNet2DConditionModel)
+    for name in UNET_ONLY:
+        assert not hasattr(cls, name), name
