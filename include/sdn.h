@@ -745,6 +745,22 @@ int sdn_image_resize_u8(const uint8_t* in, int32_t batch, int32_t in_size, int32
                         const int32_t* bounds, int32_t ksize, uint8_t* tmp, uint8_t* out, void* stream);
 int sdn_clip_normalize_u8(const uint8_t* in, int32_t batch, int32_t size, float mean_r, float mean_g, float mean_b, float std_r,
                           float std_g, float std_b, float* out, void* stream);
+/* The transform of the negative reference images (data/dataloader.py:46-78: `transforms.Resize((512, 512))` on a PIL image =
+ * `Image.resize((512, 512), BILINEAR)`, then ToTensor and Normalize(.5, .5)), for a batch of equally sized RGB images of ANY
+ * aspect ratio.
+ * sdn_image_resize_rect_u8: Pillow's two-pass 8-bit resampling, in [B, in_h, in_w, 3] -> [B, out_h, out_w, 3].  The horizontal
+ *   pass runs first (tmp [B, in_h, out_w, 3] uint8, rounded and clipped as in Pillow), the vertical one second; each axis has its
+ *   own tables (coeffs_x [out_w, ksize_x] / bounds_x [out_w, 2], coeffs_y [out_h, ksize_y] / bounds_y [out_h, 2], the format of
+ *   sdn_image_resize_u8, any filter).  An axis that keeps its length has NO pass (Pillow's need_horizontal / need_vertical): its
+ *   table pointers must be NULL, and must not be NULL otherwise; with neither pass the result is a copy.  tmp is needed only when
+ *   both passes run.  Outputs, either nullable but not both: out_u8 [B, out_h, out_w, 3], and out_f32 [B, 3, out_h, out_w] =
+ *   ((u8 / 255) - mean_c) / std_c with sdn_clip_normalize_u8's f32 operations (the same bits), written by the last pass from the
+ *   8-bit value in registers.  std_c > 0 always.  Dimensions 1..16384, ksize 1..4096; taps outside the input are not read.  No
+ *   allocation, no synchronisation. */
+int sdn_image_resize_rect_u8(const uint8_t* in, int32_t batch, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w,
+                             const int32_t* coeffs_x, const int32_t* bounds_x, int32_t ksize_x, const int32_t* coeffs_y,
+                             const int32_t* bounds_y, int32_t ksize_y, uint8_t* tmp, uint8_t* out_u8, float* out_f32, float mean_r,
+                             float mean_g, float mean_b, float std_r, float std_g, float std_b, void* stream);
 
 /* ---- T5 encoder (SD-v3 text_encoder_3: the encoder every SD-v3 SAFREE decision rests on) ---------------------------------
  * Replaces `self.text_encoder_3(input_ids, attention_mask=...)[0]` (transformers T5EncoderModel, third party), called at

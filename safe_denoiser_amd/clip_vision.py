@@ -8,7 +8,9 @@ CLIPVisionModelWithProjection takes a transformers CLIPVisionModelWithProjection
 `visual.*` keys.  Neither the OpenAI `clip` package nor torchvision is needed: for the SQUARE images the engine produces,
 torchvision's Resize(224, BICUBIC) + CenterCrop + ToTensor + Normalize on a PIL image is PIL.Image.resize((224, 224), BICUBIC)
 followed by ((u8 / 255) - mean) / std, and Pillow's 8-bit resize is integer arithmetic that sdn_image_resize_u8 reproduces bit for
-bit from coefficient tables built here in double (resize_tables).  Non-square inputs are refused.
+bit from coefficient tables built here in double (resize_tables).  Non-square inputs are refused there; resize_rect /
+resize_rect_u8 (sdn_image_resize_rect_u8) resample images of any aspect ratio with Pillow's bilinear or bicubic filter -- the
+transform of the negative reference images (safe_denoiser_amd/data.py).
 """
 from __future__ import annotations
 
@@ -40,12 +42,23 @@ def _bicubic(x: float, a: float = -0.5) -> float:
     return 0.0
 
 
-def resize_tables(in_size: int, out_size: int):
-    """Pillow's bicubic coefficient tables for one axis, in double (Python floats): (coeffs int32 [out, ksize] = the normalised taps
-    times 2^22, rounded half away from zero; bounds int32 [out, 2] = (first input index, tap count); ksize)."""
+def _bilinear(x: float) -> float:
+    x = -x if x < 0.0 else x
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+FILTERS = {"bicubic": (_bicubic, 2.0), "bilinear": (_bilinear, 1.0)}      # Pillow's (filter, support)
+
+
+def resize_tables(in_size: int, out_size: int, filter: str = "bicubic"):
+    """Pillow's coefficient tables for one axis and one of its filters, in double (Python floats): (coeffs int32 [out, ksize] = the
+    normalised taps times 2^22, rounded half away from zero; bounds int32 [out, 2] = (first input index, tap count); ksize)."""
+    if filter not in FILTERS:
+        raise _lib.SdnError(f"filter must be one of {sorted(FILTERS)}, got {filter!r}")
+    fn, radius = FILTERS[filter]
     scale = in_size / out_size
     fs = max(scale, 1.0)
-    support = 2.0 * fs
+    support = radius * fs
     ksize = int(math.ceil(support)) * 2 + 1
     ss = 1.0 / fs
     coeffs = np.zeros((out_size, ksize), dtype=np.int32)
@@ -54,7 +67,7 @@ def resize_tables(in_size: int, out_size: int):
         center = (i + 0.5) * scale
         xmin = max(0, int(center - support + 0.5))
         xmax = min(in_size, int(center + support + 0.5))
-        w = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax - xmin)]
+        w = [fn((x + xmin - center + 0.5) * ss) for x in range(xmax - xmin)]
         total = 0.0
         for v in w:                                                # summed in tap order, as Pillow does
             total += v
@@ -69,11 +82,11 @@ def resize_tables(in_size: int, out_size: int):
 _TABLES: dict = {}
 
 
-def _device_tables(in_size: int, out_size: int, device):
-    key = (in_size, out_size, str(device))
+def _device_tables(in_size: int, out_size: int, device, filter: str = "bicubic"):
+    key = (in_size, out_size, filter, str(device))
     t = _TABLES.get(key)
     if t is None:
-        coeffs, bounds, ksize = resize_tables(in_size, out_size)
+        coeffs, bounds, ksize = resize_tables(in_size, out_size, filter)
         t = (torch.from_numpy(coeffs).to(device), torch.from_numpy(bounds).to(device), ksize)
         _TABLES[key] = t
     return t
@@ -123,6 +136,44 @@ def resize_u8(images_u8: torch.Tensor, size: int = 224) -> torch.Tensor:
     _lib.check(_lib.lib().sdn_image_resize_u8(t.data_ptr(), b, s, size, coeffs.data_ptr(), bounds.data_ptr(), ksize, tmp.data_ptr(),
                                               out.data_ptr(), _lib.stream_ptr()), "sdn_image_resize_u8")
     return out
+
+
+def resize_rect(images_u8: torch.Tensor, size, filter: str = "bilinear", mean=None, std=None, want_u8: bool = True):
+    """PIL.Image.resize((out_w, out_h), filter) of every image of a uint8 GPU tensor [B, H, W, 3], any aspect ratio, for
+    size = (out_h, out_w): (uint8 [B, out_h, out_w, 3] or None, f32 [B, 3, out_h, out_w] = ((u8 / 255) - mean) / std or None when
+    mean is None).  The f32 planes are written by the resize's last pass; they are normalize_u8's bits of the uint8 result."""
+    _lib.require_gpu()
+    t = images_u8
+    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3 or not t.is_cuda:
+        raise _lib.SdnError("images must be a uint8 GPU tensor [B, H, W, 3]")
+    if filter not in FILTERS:
+        raise _lib.SdnError(f"filter must be one of {sorted(FILTERS)}, got {filter!r}")
+    out_h, out_w = (int(v) for v in size)
+    want_f32 = mean is not None
+    if not want_u8 and not want_f32:
+        raise _lib.SdnError("nothing to compute: want_u8 is False and no mean / std is given")
+    if want_f32 and std is None:
+        raise _lib.SdnError("std is required with mean")
+    t = t.contiguous()
+    b, h, w = t.shape[0], t.shape[1], t.shape[2]
+    dev = t.device
+    cx, bx, kx = _device_tables(w, out_w, dev, filter) if w != out_w else (None, None, 0)      # an unchanged axis has no pass
+    cy, by, ky = _device_tables(h, out_h, dev, filter) if h != out_h else (None, None, 0)
+    tmp = torch.empty((b, h, out_w, 3), dtype=torch.uint8, device=dev) if cx is not None and cy is not None else None
+    u8 = torch.empty((b, out_h, out_w, 3), dtype=torch.uint8, device=dev) if want_u8 else None
+    f32 = torch.empty((b, 3, out_h, out_w), dtype=torch.float32, device=dev) if want_f32 else None
+    m = [float(v) for v in mean] if want_f32 else [0.0, 0.0, 0.0]
+    s = [float(v) for v in std] if want_f32 else [1.0, 1.0, 1.0]
+    _lib.check(_lib.lib().sdn_image_resize_rect_u8(t.data_ptr(), b, h, w, out_h, out_w, _lib.dptr(cx), _lib.dptr(bx), kx, _lib.dptr(cy),
+                                                   _lib.dptr(by), ky, _lib.dptr(tmp), _lib.dptr(u8), _lib.dptr(f32), *m, *s,
+                                                   _lib.stream_ptr()), "sdn_image_resize_rect_u8")
+    return u8, f32
+
+
+def resize_rect_u8(images_u8: torch.Tensor, size, filter: str = "bilinear") -> torch.Tensor:
+    """PIL.Image.resize((out_w, out_h), BILINEAR | BICUBIC) of every image of a uint8 GPU tensor [B, H, W, 3], bit for bit;
+    size = (out_h, out_w)."""
+    return resize_rect(images_u8, size, filter)[0]
 
 
 def normalize_u8(images_u8: torch.Tensor, mean=CLIP_MEAN, std=CLIP_STD) -> torch.Tensor:

@@ -1,7 +1,7 @@
 // Building blocks of the CLIP ViT vision tower (transformers CLIPVisionModelWithProjection, third party; the OpenAI ViT-L/14 image
 // encoder behind the reference's Q16 classifier) and of CLIP's image preprocessing: the patch rows the patch convolution reads as
 // a GEMM operand, the embedding row kernel (class token / patch projection + position embedding, then pre_layrnorm), post_layernorm
-// on the class rows, Pillow's 8-bit bicubic resampling and the uint8 -> normalised f32 map.  The encoder layers are plan GEMMs,
+// on the class rows, Pillow's 8-bit resampling (square and rectangular) and the uint8 -> normalised f32 map.  The encoder layers are plan GEMMs,
 // row LayerNorms and the d = 64 attention kernel (sdn_plan_vision.hip).
 #include <math.h>
 
@@ -164,6 +164,56 @@ k_clip_normalize(const unsigned char* __restrict__ in, long pixels, long plane, 
   }
 }
 
+// The LAST pass of a rectangular resize (or, with coeffs == nullptr, the copy Pillow makes when neither axis changes length): the
+// arithmetic of k_resize_pass, then the clipped 8-bit value goes from registers to out_u8 [B, out_h, out_w, 3] and / or, through
+// k_clip_normalize's f32 operations in their order, to the planes out_f32 [B, 3, out_h, out_w].  One thread per output pixel, x
+// fastest: a wave stores 64 consecutive floats of each plane.
+__global__ void __launch_bounds__(THREADS)
+k_resize_last(const unsigned char* __restrict__ in, unsigned char* __restrict__ out_u8, float* __restrict__ out_f32, Norm3 nm,
+              const int* __restrict__ coeffs, const int* __restrict__ bounds, int ksize, long total, int in_len, int vertical, int in_h,
+              int in_w, int out_h, int out_w) {
+  const long plane = (long)out_h * out_w;
+  for (long e = (long)blockIdx.x * THREADS + threadIdx.x; e < total; e += (long)gridDim.x * THREADS) {
+    const long b = e / plane;
+    const int r = (int)(e - b * plane), y = r / out_w, x = r - y * out_w;
+    int v[3];
+    if (coeffs) {
+      const int i = vertical ? y : x;
+      int lo = bounds[2 * i], cnt = bounds[2 * i + 1];
+      if (lo < 0) lo = 0;
+      if (cnt > ksize) cnt = ksize;
+      if (cnt > in_len - lo) cnt = in_len - lo;
+      const int* k = coeffs + (long)i * ksize;
+      const unsigned char* src = in + ((b * in_h + (vertical ? lo : y)) * (long)in_w + (vertical ? x : lo)) * 3;
+      const long step = vertical ? (long)in_w * 3 : 3;
+      int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
+      for (int t = 0; t < cnt; ++t) {
+        const int w = k[t];
+        s0 += (int)src[0] * w; s1 += (int)src[1] * w; s2 += (int)src[2] * w;
+        src += step;
+      }
+      s0 >>= 22; s1 >>= 22; s2 >>= 22;
+      v[0] = s0 < 0 ? 0 : (s0 > 255 ? 255 : s0);
+      v[1] = s1 < 0 ? 0 : (s1 > 255 ? 255 : s1);
+      v[2] = s2 < 0 ? 0 : (s2 > 255 ? 255 : s2);
+    } else {
+      const unsigned char* src = in + e * 3;                           // same shape in and out
+      v[0] = src[0]; v[1] = src[1]; v[2] = src[2];
+    }
+    if (out_u8) {
+      unsigned char* dst = out_u8 + e * 3;
+      dst[0] = (unsigned char)v[0]; dst[1] = (unsigned char)v[1]; dst[2] = (unsigned char)v[2];
+    }
+    if (out_f32) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float u = (float)(unsigned char)v[c] / 255.0f;
+        out_f32[(b * 3 + c) * plane + r] = (u - nm.mean[c]) / nm.stdv[c];
+      }
+    }
+  }
+}
+
 unsigned grid_for(long items) {
   long g = (items + THREADS - 1) / THREADS;
   return (unsigned)(g > 16384 ? 16384 : (g < 1 ? 1 : g));
@@ -238,6 +288,47 @@ extern "C" int sdn_image_resize_u8(const uint8_t* in, int32_t batch, int32_t in_
   hipLaunchKernelGGL(k_resize_pass, dim3(grid_for(n1)), dim3(THREADS), 0, st, in, tmp, coeffs, bounds, ksize, n1, T, S, 0, S, S, S, T);
   hipLaunchKernelGGL(k_resize_pass, dim3(grid_for(n2)), dim3(THREADS), 0, st, (const unsigned char*)tmp, out, coeffs, bounds, ksize, n2, T, S, 1,
                      S, T, T, T);
+  return sdn_launch_status();
+}
+
+extern "C" int sdn_image_resize_rect_u8(const uint8_t* in, int32_t batch, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w,
+                                        const int32_t* coeffs_x, const int32_t* bounds_x, int32_t ksize_x, const int32_t* coeffs_y,
+                                        const int32_t* bounds_y, int32_t ksize_y, uint8_t* tmp, uint8_t* out_u8, float* out_f32,
+                                        float mean_r, float mean_g, float mean_b, float std_r, float std_g, float std_b, void* stream) {
+  auto dim_ok = [](int32_t d) { return d >= 1 && d <= 16384; };
+  if (!in || (!out_u8 && !out_f32) || batch < 0 || !dim_ok(in_h) || !dim_ok(in_w) || !dim_ok(out_h) || !dim_ok(out_w) ||
+      !(std_r > 0.f) || !(std_g > 0.f) || !(std_b > 0.f) || !aligned(out_f32, 4))
+    return SDN_E_INVALID;
+  // an axis that keeps its length has no pass and no tables; one that changes needs both tables
+  const bool horizontal = in_w != out_w, vertical = in_h != out_h;
+  if (horizontal ? (!coeffs_x || !bounds_x || ksize_x <= 0 || ksize_x > 4096 || !aligned(coeffs_x, 4) || !aligned(bounds_x, 4))
+                 : (coeffs_x || bounds_x))
+    return SDN_E_INVALID;
+  if (vertical ? (!coeffs_y || !bounds_y || ksize_y <= 0 || ksize_y > 4096 || !aligned(coeffs_y, 4) || !aligned(bounds_y, 4))
+               : (coeffs_y || bounds_y))
+    return SDN_E_INVALID;
+  if (horizontal && vertical && !tmp) return SDN_E_INVALID;
+  if (batch == 0) return SDN_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const Norm3 nm{{mean_r, mean_g, mean_b}, {std_r, std_g, std_b}};
+  const long n_out = (long)batch * out_h * out_w;
+  const dim3 grid(grid_for(n_out)), blk(THREADS);
+  if (horizontal && vertical) {
+    const long n1 = (long)batch * in_h * out_w;
+    hipLaunchKernelGGL(k_resize_pass, dim3(grid_for(n1)), blk, 0, st, in, tmp, coeffs_x, bounds_x, ksize_x, n1, out_w, in_w, 0, in_h, in_w,
+                       in_h, out_w);
+    hipLaunchKernelGGL(k_resize_last, grid, blk, 0, st, (const unsigned char*)tmp, out_u8, out_f32, nm, coeffs_y, bounds_y, ksize_y, n_out,
+                       in_h, 1, in_h, out_w, out_h, out_w);
+  } else if (horizontal) {
+    hipLaunchKernelGGL(k_resize_last, grid, blk, 0, st, in, out_u8, out_f32, nm, coeffs_x, bounds_x, ksize_x, n_out, in_w, 0, in_h, in_w,
+                       out_h, out_w);
+  } else if (vertical) {
+    hipLaunchKernelGGL(k_resize_last, grid, blk, 0, st, in, out_u8, out_f32, nm, coeffs_y, bounds_y, ksize_y, n_out, in_h, 1, in_h, in_w,
+                       out_h, out_w);
+  } else {
+    hipLaunchKernelGGL(k_resize_last, grid, blk, 0, st, in, out_u8, out_f32, nm, (const int*)nullptr, (const int*)nullptr, 0, n_out, 0, 0,
+                       in_h, in_w, out_h, out_w);
+  }
   return sdn_launch_status();
 }
 

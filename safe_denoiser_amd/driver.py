@@ -1,5 +1,6 @@
 """Driver-side data formats either side of the hot path: the three-layer configuration the
-reference's drivers read, and the artefacts they write.  Everything here is host logic (no GPU call).
+reference's drivers read, and the artefacts they write.  Everything here is host logic (no GPU call) except `build_repellency`,
+the drivers' repellency block (run_nudity.py:294-325): negative images -> VAE encoder -> `proj_ref` -> the processor run_job takes.
 
 Configuration, in the reference's own order (run_nudity.py:534-625):
   1. `--config` JSON is parsed FIRST (parse_known_args, :538-540) and supplies the DEFAULT of every other flag;
@@ -142,6 +143,50 @@ def repellency_kwargs(task_config: Mapping[str, Any], num_inference_steps: int, 
     return dict(name=rc["method"], num_timesteps=num_inference_steps, max_idx=len(scheduler.betas),
                 beta_min=scheduler.beta_start, beta_max=scheduler.beta_end, n_embed=rc["n_embed"], scheduler=scheduler,
                 **rc["params"])
+
+
+def build_repellency(args, pipe, task_config: Mapping[str, Any], get_repellency_method: Optional[Callable] = None, eager: bool = False,
+                     rank: Optional[int] = None, world: Optional[int] = None, device=None, decode_threads: Optional[int] = None):
+    """The repellency block of the reference's main() (run_nudity.py:294-325): the task YAML's `data:` section -> dataset ->
+    reference images -> `get_repellency_method(method, ref_data=..., embed_fn=vae embed_fn, forward_fn=scheduler.add_noise, ...)`;
+    the result is run_job's `repellency_processor`.  `pipe` needs `.vae` (with encoder weights) and `.scheduler`.
+    The images are a lazy set by default -- `project` embeds `n_embed` at a time and the [M, 3, 512, 512] stack is never resident;
+    `eager=True` builds the tensor the reference builds (same proj_ref bits under the same global seed).
+    `get_repellency_method`: the registry function of the front-end to use (default repellency_methods_threshold's; the CoPro /
+    SD-v3 callers pass repellency_methods_fast's / repellency_methods_fast_sdv3's).
+    With W > 1 ranks (default: the initialised process group) only rank 0 reads images and writes the cache file; the others
+    receive proj_ref through dist.broadcast_proj_ref and build their processor around it."""
+    from . import data as _data, dist as _dist
+    _ = task_config["mean_processor"]                           # required and unused (:297)
+    if get_repellency_method is None:
+        from .repellency.repellency_methods_threshold import get_repellency_method
+    if rank is None or world is None:
+        import torch.distributed as td
+        rank, world = (td.get_rank(), td.get_world_size()) if td.is_initialized() else (0, 1)
+    kw = repellency_kwargs(task_config, args.num_inference_steps, pipe.scheduler)
+    common = dict(embed_fn=pipe.vae.embed_fn(), forward_fn=pipe.scheduler.add_noise)
+    proc = None
+    if rank == 0:
+        data_config = dict(task_config["data"])
+        if device is not None:
+            data_config["device"] = device
+        transform = _data.get_transform(**data_config)
+        for key in ("size", "device"):                              # the engine's own transform keys
+            data_config.pop(key, None)
+        dataset = _data.get_dataset(**data_config, transforms=transform)
+        loader = _data.get_dataloader(dataset, batch_size=1, num_workers=0, train=False, decode_threads=decode_threads)
+        ref_imgs = _data.get_all_imgs(loader, lazy=not eager)
+        try:
+            proc = get_repellency_method(ref_data=ref_imgs, **common, **kw)
+        finally:
+            loader.close()
+    if world > 1:
+        import torch
+        dev = proc.proj_refs.device if proc is not None else torch.device(device or "cuda")
+        refs = _dist.broadcast_proj_ref(proc.proj_refs if proc is not None else None, dev)
+        if proc is None:
+            proc = get_repellency_method(ref_data=refs, proj_refs=refs, **common, **kw)
+    return proc
 
 
 def safree_dict(args, logger=None) -> dict:

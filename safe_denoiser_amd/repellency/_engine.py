@@ -54,7 +54,9 @@ class RepellencyEngine:
         self.epsilon = kwargs.get("epsilon", 1e-8)
         self.proj_ref_path = kwargs.get("proj_ref_path", None)
         self.cache_proj_ref = kwargs.get("cache_proj_ref", False)
-        if self.cache_proj_ref:
+        if kwargs.get("proj_refs", None) is not None:
+            self.proj_refs = kwargs["proj_refs"]            # built elsewhere (rank 0's, broadcast): nothing is embedded or read here
+        elif self.cache_proj_ref:
             self.proj_refs = self.import_proj_ref(self.proj_ref_path)
         else:
             self.proj_refs = self.set_proj_ref()
@@ -69,7 +71,7 @@ class RepellencyEngine:
         if n > self.n_embed:
             emb = torch.cat([self.embed_fn(data[i:min(i + self.n_embed, n)]) for i in range(0, n, self.n_embed)], 0)
         else:
-            emb = self.embed_fn(data)
+            emb = self.embed_fn(data if isinstance(data, torch.Tensor) else data[0:n])   # a lazy set (data.LazyRefImages): its one chunk
         emb = emb / torch.norm(emb, dim=1, keepdim=True)
         return emb.float() if self.float_refs else emb
 
