@@ -18,9 +18,35 @@ namespace sdn_plan {
 // which model a handle is: set once by its sdn_*_create, read by every entry point's guard and by get_plan
 enum ModelKind { UNET, MMDIT, VAE_DECODER, VAE_ENCODER, CLIP, CLIP_PROJ, T5, CLIP_VISION };
 
-enum Space { SP_NONE = 0, SP_W = 1, SP_WS = 2, SP_LATENTS = 3, SP_TEXT = 4, SP_OUT = 5, SP_POOLED = 6,
-             SP_KV = 7 };   // SP_KV: the workspace's persistent tail (text K / V slots: written by one op, read by one op, never recycled)
+enum Space { SP_NONE = 0, SP_W = 1, SP_WS = 2, SP_IN = 3, SP_TEXT = 4, SP_OUT = 5, SP_POOLED = 6, SP_KV = 7, SP_OUT2 = 8 };
+// SP_IN / SP_OUT / SP_OUT2: a Call's primary input and its two outputs; SP_KV: the workspace's persistent tail (text K / V slots: written by one op, read by one op, never recycled)
 struct Ref { int space = SP_NONE; int64_t off = 0; };
+
+// Everything one forward is given.  An entry point fills the operands its plan names and leaves the rest null; c(ref) is the address
+// a plan-time Ref names in this call.
+struct Call {
+  const void* weights; void* workspace; size_t workspace_bytes; int32_t batch; void* stream;
+  const void *in = nullptr, *text = nullptr, *pooled = nullptr;   // in: latents, token ids, pixels or image; pooled: MMDiT
+  void *out = nullptr, *out2 = nullptr;     // out2: text_embeds / image_embeds; the vision tower's out is nullable (its copy is skipped)
+  float scalar = 0.f; int n = 0;            // scalar: timestep, or a VAE decoder's latent_scale; n: T5 sequence length
+  const int32_t* mask = nullptr;            // key-padding mask (nullable; CLIP and T5)
+  int64_t out_bs = 0, out_rs = 0, out2_rs = 0;   // batch / row stride of out and row stride of out2 (elements), where the caller chooses them
+  int64_t kv_base = 0;                      // not the caller's: run_plan's copy carries its plan's SP_KV base
+  Call(const void* w, void* ws, size_t ws_bytes, int32_t b, void* s) : weights(w), workspace(ws), workspace_bytes(ws_bytes), batch(b), stream(s) {}
+  const char* operator()(const Ref& r) const {
+    switch (r.space) {
+      case SP_W: return (const char*)weights + r.off;
+      case SP_WS: return (const char*)workspace + r.off;
+      case SP_KV: return (const char*)workspace + kv_base + r.off;
+      case SP_IN: return (const char*)in + r.off;
+      case SP_TEXT: return (const char*)text + r.off;
+      case SP_OUT: return (const char*)out + r.off;
+      case SP_OUT2: return (const char*)out2 + r.off;
+      case SP_POOLED: return (const char*)pooled + r.off;
+      default: return nullptr;
+    }
+  }
+};
 
 enum OpKind { OP_TEMB, OP_CONV_IN, OP_GEMM, OP_GN, OP_LN, OP_ATTN, OP_PATCHIFY, OP_UNPATCHIFY, OP_LATENT_MIX, OP_SOFTMAX,
               OP_TRANSPOSE, OP_GAUSS, OP_REPEAT, OP_CLIP_EMBED, OP_MATTN, OP_ROWSTATS, OP_FFN, OP_SPLIT3,
@@ -38,7 +64,7 @@ struct Op {
   int x3t = 0;               // bf16x3 plan: this GEMM runs on sdn_gemm_bf16 over triple operands (gd holds the EXPANDED K / Cin)
   int pair_in = 0;           // bf16x3 plan: attention whose q / k / v are column blocks of ONE hi | lo pair-row buffer (sdn_attention_x3_pairs)
   int tri_out = 0;           // bf16x3 plan: GroupNorm / LayerNorm / attention write the bf16 hi|lo|hi triple a GEMM will read
-  int dyn_ldc = 0;           // projected CLIP plan: the output's leading dimension is the caller's row stride of this forward
+  int dyn_ldc = 0;           // projected CLIP plan: the output's leading dimension is the call's out2_rs
   int n1 = 0, mod = 0, ld_mod = 0, patch = 0;
   // GN / LN / conv_in / attention scalars
   int batch = 0, hw = 0, c1 = 0, c2 = 0, groups = 0, silu = 0;
@@ -120,12 +146,9 @@ struct sdn_unet {
   sdn_mmdit_config mcfg;
   sdn_vae_config vcfg;
   sdn_clip_config ccfg;
-  const void* clip_mask = nullptr;      // key-padding mask of the forward in flight (nullable; CLIP and T5)
   sdn_clip_proj_config pcfg;            // CLIP_PROJ: ccfg mirrors its encoder fields (same layers as CLIP)
-  int64_t proj_hbs = 0, proj_hrs = 0, proj_ers = 0;   // output strides (elements) of the sdn_clip_proj_forward in flight
   sdn_t5_config tcfg;
   sdn_clip_vision_config vis;           // CLIP_VISION
-  bool vision_hidden = true;            // CLIP_VISION: the forward in flight was given a last_hidden_state buffer
   std::vector<sdn_param_info> params;
   std::map<std::string, int> param_index;
   int64_t weight_bytes = 0;
@@ -278,10 +301,8 @@ struct Builder {
 
 // n: the sequence length of a T5 plan (ignored by every other plan); 0 = the longest one (512), which bounds the workspace of any n
 Plan* get_plan(sdn_unet* u, int batch, int n = 0);
-const char* resolve(const Ref& r, const char* w, const char* ws, const char* lat, const char* text, const char* out,
-                    const char* pooled, const char* kv = nullptr);
-int run_plan(sdn_unet* u, const void* weights, const float* latents, float timestep, const void* text,
-             const void* pooled, float* out, int32_t batch, void* workspace, size_t workspace_bytes, void* stream, int n = 0);
+// checks what every kind needs (handle, weights, workspace, batch, plan, workspace size); an entry point rejects a null operand of its own plan first
+int run_plan(sdn_unet* u, const Call& c);
 void drop_graphs(sdn_unet* u);
 
 }  // namespace sdn_plan

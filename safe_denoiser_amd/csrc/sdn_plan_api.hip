@@ -218,61 +218,60 @@ double sdn_unet_flops(sdn_unet* u, int32_t batch, double* attn) {
   return p->flops;
 }
 
-int sdn_vae_decode(sdn_unet* v, const void* weights, const float* latents, float latent_scale, float* image, int32_t batch,
-                   void* workspace, size_t workspace_bytes, void* stream) {
-  if (!v || v->kind != VAE_DECODER || batch < 0) return SDN_E_INVALID;
+// Runs a VAE plan over `batch` images in chunks of vae_chunk(): in / out advance by in_n / out_n floats per image.
+static int vae_run(sdn_unet* v, Call call, const float* in, int64_t in_n, float* out, int64_t out_n, int32_t batch) {
+  if (batch < 0 || (batch > 0 && (!in || !out))) return SDN_E_INVALID;
   const int cap = vae_chunk(v);
   if (cap == 0) return SDN_E_INVALID;                              // a single image already exceeds the 32-bit offsets
-  const sdn_vae_config& c = v->vcfg;
-  const int64_t side = (int64_t)c.sample_size << (c.n_levels - 1);
-  const int64_t lat_n = (int64_t)c.latent_channels * c.sample_size * c.sample_size, img_n = (int64_t)c.out_channels * side * side;
   for (int lo = 0; lo < batch; lo += cap) {
-    const int nb = batch - lo < cap ? batch - lo : cap;
-    const int rc = run_plan(v, weights, latents + lo * lat_n, latent_scale, weights /* no text operand */, nullptr, image + lo * img_n,
-                            nb, workspace, workspace_bytes, stream);
+    call.batch = batch - lo < cap ? batch - lo : cap;
+    call.in = in + lo * in_n; call.out = out + lo * out_n;
+    const int rc = run_plan(v, call);
     if (rc != SDN_OK) return rc;
   }
   return SDN_OK;
+}
+
+int sdn_vae_decode(sdn_unet* v, const void* weights, const float* latents, float latent_scale, float* image, int32_t batch,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+  if (!v || v->kind != VAE_DECODER) return SDN_E_INVALID;
+  const sdn_vae_config& c = v->vcfg;
+  const int64_t side = (int64_t)c.sample_size << (c.n_levels - 1);
+  Call call(weights, workspace, workspace_bytes, 0, stream);
+  call.scalar = latent_scale;
+  return vae_run(v, call, latents, (int64_t)c.latent_channels * c.sample_size * c.sample_size, image, (int64_t)c.out_channels * side * side, batch);
 }
 
 int sdn_vae_encode(sdn_unet* v, const void* weights, const float* image, float* moments, int32_t batch, void* workspace,
                    size_t workspace_bytes, void* stream) {
-  if (!v || v->kind != VAE_ENCODER || batch < 0) return SDN_E_INVALID;
-  const int cap = vae_chunk(v);
-  if (cap == 0) return SDN_E_INVALID;
+  if (!v || v->kind != VAE_ENCODER) return SDN_E_INVALID;
   const sdn_vae_config& c = v->vcfg;
   const int64_t side = (int64_t)c.sample_size << (c.n_levels - 1);
-  const int64_t img_n = (int64_t)c.out_channels * side * side, mom_n = (int64_t)2 * c.latent_channels * c.sample_size * c.sample_size;
-  for (int lo = 0; lo < batch; lo += cap) {
-    const int nb = batch - lo < cap ? batch - lo : cap;
-    const int rc = run_plan(v, weights, image + lo * img_n, 1.0f, weights /* no text operand */, nullptr, moments + lo * mom_n, nb,
-                            workspace, workspace_bytes, stream);
-    if (rc != SDN_OK) return rc;
-  }
-  return SDN_OK;
+  return vae_run(v, Call(weights, workspace, workspace_bytes, 0, stream), image, (int64_t)c.out_channels * side * side, moments,
+                 (int64_t)2 * c.latent_channels * c.sample_size * c.sample_size, batch);
 }
 
 int sdn_clip_forward(sdn_unet* m, const void* weights, const int32_t* input_ids, const int32_t* attention_mask,
                      void* last_hidden_state, int32_t batch, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!m || m->kind != CLIP) return SDN_E_INVALID;
-  m->clip_mask = attention_mask;
-  return run_plan(m, weights, (const float*)input_ids, 0.f, weights /* no text operand */, nullptr, (float*)last_hidden_state,
-                  batch, workspace, workspace_bytes, stream);
+  if (!m || m->kind != CLIP || !input_ids || !last_hidden_state) return SDN_E_INVALID;
+  Call call(weights, workspace, workspace_bytes, batch, stream);
+  call.in = input_ids; call.mask = attention_mask; call.out = last_hidden_state;
+  return run_plan(m, call);
 }
 
 int sdn_clip_proj_forward(sdn_unet* m, const void* weights, const int32_t* input_ids, void* hidden, int64_t hidden_batch_stride,
                           int64_t hidden_row_stride, void* text_embeds, int64_t embeds_row_stride, int32_t batch, void* workspace,
                           size_t workspace_bytes, void* stream) {
-  if (!m || m->kind != CLIP_PROJ || !hidden || !text_embeds) return SDN_E_INVALID;
+  if (!m || m->kind != CLIP_PROJ || !input_ids || !hidden || !text_embeds) return SDN_E_INVALID;
   const sdn_clip_proj_config& c = m->pcfg;
   if (hidden_row_stride < c.hidden_size || hidden_batch_stride < (int64_t)c.max_position_embeddings * hidden_row_stride ||
       embeds_row_stride < c.projection_dim || embeds_row_stride > 0x7fffffff || (hidden_row_stride & 7) || (hidden_batch_stride & 7) ||
       (embeds_row_stride & 7) || (reinterpret_cast<uintptr_t>(hidden) & 15) || (reinterpret_cast<uintptr_t>(text_embeds) & 15))
     return SDN_E_INVALID;
-  m->clip_mask = nullptr;
-  m->proj_hbs = hidden_batch_stride; m->proj_hrs = hidden_row_stride; m->proj_ers = embeds_row_stride;
-  return run_plan(m, weights, (const float*)input_ids, 0.f, weights /* no text operand */, text_embeds, (float*)hidden, batch,
-                  workspace, workspace_bytes, stream);
+  Call call(weights, workspace, workspace_bytes, batch, stream);
+  call.in = input_ids; call.out = hidden; call.out2 = text_embeds;
+  call.out_bs = hidden_batch_stride; call.out_rs = hidden_row_stride; call.out2_rs = embeds_row_stride;
+  return run_plan(m, call);
 }
 
 size_t sdn_t5_workspace_bytes(sdn_unet* m, int32_t batch, int32_t n) {
@@ -290,23 +289,27 @@ double sdn_t5_flops(sdn_unet* m, int32_t batch, int32_t n, double* attn) {
 
 int sdn_t5_forward(sdn_unet* m, const void* weights, const int32_t* input_ids, const int32_t* attention_mask, int32_t n,
                    void* out, int32_t batch, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!m || m->kind != T5 || n < 2 || n > 512 || batch > (1 << 20)) return SDN_E_INVALID;
-  m->clip_mask = attention_mask;
-  return run_plan(m, weights, (const float*)input_ids, 0.f, weights /* no text operand */, nullptr, (float*)out, batch, workspace,
-                  workspace_bytes, stream, n);
+  if (!m || m->kind != T5 || n < 2 || n > 512 || batch > (1 << 20) || !input_ids || !out) return SDN_E_INVALID;
+  Call call(weights, workspace, workspace_bytes, batch, stream);
+  call.in = input_ids; call.mask = attention_mask; call.n = n; call.out = out;
+  return run_plan(m, call);
 }
 
 int sdn_unet_forward(sdn_unet* u, const void* weights, const float* latents, float timestep, const void* text,
                      float* out, int32_t batch, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!u || u->kind != UNET) return SDN_E_INVALID;
-  return run_plan(u, weights, latents, timestep, text, nullptr, out, batch, workspace, workspace_bytes, stream);
+  if (!u || u->kind != UNET || !latents || !text || !out) return SDN_E_INVALID;
+  Call call(weights, workspace, workspace_bytes, batch, stream);
+  call.in = latents; call.scalar = timestep; call.text = text; call.out = out;
+  return run_plan(u, call);
 }
 
 int sdn_mmdit_forward(sdn_unet* u, const void* weights, const float* latents, float timestep, const void* text,
                       const void* pooled, float* out, int32_t batch, void* workspace, size_t workspace_bytes,
                       void* stream) {
-  if (!u || u->kind != MMDIT || !pooled) return SDN_E_INVALID;
-  return run_plan(u, weights, latents, timestep, text, pooled, out, batch, workspace, workspace_bytes, stream);
+  if (!u || u->kind != MMDIT || !latents || !text || !pooled || !out) return SDN_E_INVALID;
+  Call call(weights, workspace, workspace_bytes, batch, stream);
+  call.in = latents; call.scalar = timestep; call.text = text; call.pooled = pooled; call.out = out;
+  return run_plan(u, call);
 }
 
 void sdn_unet_set_text_version(sdn_unet* u, uint64_t version) {

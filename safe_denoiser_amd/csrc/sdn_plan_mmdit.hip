@@ -101,7 +101,7 @@ void Builder::build_mmdit() {
 
   // ---- token streams ----
   Act patches = act((int64_t)B * N, KP);
-  { Op o; o.kind = OP_PATCHIFY; o.batch = B; o.c1 = c.in_channels; o.hw = S; o.patch = ps; o.a = Ref{SP_LATENTS, 0}; o.out = R(patches);
+  { Op o; o.kind = OP_PATCHIFY; o.batch = B; o.c1 = c.in_channels; o.hw = S; o.patch = ps; o.a = Ref{SP_IN, 0}; o.out = R(patches);
     o.bytes = (double)B * N * KP * (4.0 + es); snprintf(o.label, sizeof(o.label), es == 4 ? "k_patchify_f32" : "k_patchify"); plan->ops.push_back(o); }
   Act x = act((int64_t)B * N, C, N);
   gemm_ex((int64_t)B * N, C, KP, R(patches), pew, peb, R(x), SDN_ACT_NONE, pos, SDN_OUT_BF16, Ref(), Ref(), N, 0, 1);

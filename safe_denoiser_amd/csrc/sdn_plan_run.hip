@@ -1,22 +1,9 @@
-// Launch planner, execution: the interpreter that launches a plan's ops (one function per storage class), the chunked GEMM launch of
-// the bf16x3 plan, run_plan() with hipGraph capture / replay and text K / V reuse, and the readers of a profiled forward.
+// Launch planner, execution: the interpreter that launches a plan's ops (one function per storage class) on the operands of one Call (what
+// differs between two forwards of a handle is read from it, never from the handle), the chunked GEMM launch of the bf16x3 plan,
+// run_plan() with hipGraph capture / replay and text K / V reuse, and the readers of a profiled forward.
 #include "sdn_plan.h"
 
 namespace sdn_plan {
-
-const char* resolve(const Ref& r, const char* w, const char* ws, const char* lat, const char* text, const char* out,
-                    const char* pooled, const char* kv) {
-  switch (r.space) {
-    case SP_W: return w + r.off;
-    case SP_WS: return ws + r.off;
-    case SP_KV: return kv + r.off;
-    case SP_LATENTS: return lat + r.off;
-    case SP_TEXT: return text + r.off;
-    case SP_OUT: return out + r.off;
-    case SP_POOLED: return pooled + r.off;
-    default: return nullptr;
-  }
-}
 
 // A GEMM of the bf16x3 plan on sdn_gemm_bf16 (triple operands, expanded weights).  The LDS-DMA tiles address each operand with
 // 31-bit byte offsets, and a triple is 1.5 x its f32 tensor: the launch is cut into row chunks (whole samples for a conv) that
@@ -69,19 +56,13 @@ static int launch_x3t_gemm(const Op& o, const char* a, const char* w, const floa
   return SDN_OK;
 }
 
-// The operands of the forward in flight: P(ref) is the address a plan-time Ref names.
-struct Operands {
-  const char *W, *WS, *L, *T, *O, *PL, *KV;
-  const char* operator()(const Ref& r) const { return resolve(r, W, WS, L, T, O, PL, KV); }
-};
-
 // One op of a plan in the fp32-storage modes: same plan, fp32 operators (sdn_f32.hip); x3 = bf16x3 contractions (sdn_gemm_x3 /
 // sdn_attention_x3).  t_dev != nullptr: the timestep is read from device memory (graph mode).
-static int launch_op_f32(sdn_unet* u, const Op& o, const Operands& P, bool x3, float timestep, const float* t_dev, void* stream) {
+static int launch_op_f32(const sdn_unet* u, const Op& o, const Call& P, bool x3, const float* t_dev, void* stream) {
   int rc = SDN_OK;
   switch (o.kind) {
     case OP_TEMB:
-      rc = sdn_temb_f32(timestep, t_dev, o.batch, o.c1, (void*)P(o.out), stream);
+      rc = sdn_temb_f32(P.scalar, t_dev, o.batch, o.c1, (void*)P(o.out), stream);
       break;
     case OP_CONV_IN:
       rc = sdn_conv_in_f32((const float*)P(o.a), P(o.w), (const float*)P(o.bias), o.batch, o.c1, o.hw, o.hw, o.c2, (void*)P(o.out), stream);
@@ -89,7 +70,7 @@ static int launch_op_f32(sdn_unet* u, const Op& o, const Operands& P, bool x3, f
     case OP_GEMM:
       if (o.x3t) { rc = launch_x3t_gemm(o, P(o.a), P(o.w), (const float*)P(o.bias), (const float*)P(o.rowbias), P(o.residual), (void*)P(o.out), stream); break; }
       if (o.dyn_ldc) {
-        sdn_gemm_desc gd = o.gd; gd.ldc = (int)u->proj_ers;
+        sdn_gemm_desc gd = o.gd; gd.ldc = (int)P.out2_rs;
         rc = (x3 ? sdn_gemm_x3 : sdn_gemm_f32)(&gd, P(o.a), nullptr, P(o.w), nullptr, nullptr, nullptr, nullptr, (void*)P(o.out), stream);
         break;
       }
@@ -153,10 +134,10 @@ static int launch_op_f32(sdn_unet* u, const Op& o, const Operands& P, bool x3, f
                              u->pcfg.eos_token_id, o.eps, (void*)P(o.out), nullptr, stream);
       break;
     case OP_COPY_ROWS:
-      rc = sdn_copy_rows_strided(P(o.a), o.batch, o.hw, o.c1, 4, (void*)P(o.out), u->proj_hbs, u->proj_hrs, stream);
+      rc = sdn_copy_rows_strided(P(o.a), o.batch, o.hw, o.c1, 4, (void*)P(o.out), P.out_bs, P.out_rs, stream);
       break;
     case OP_MATTN:                               // 1.7 % of the encoder's FLOPs: exact f32 products in both fp32-storage modes
-      rc = sdn_masked_attention_f32(P(o.a), P(o.k), P(o.v), (void*)P(o.out), (const int32_t*)u->clip_mask, 1, o.batch, o.heads,
+      rc = sdn_masked_attention_f32(P(o.a), P(o.k), P(o.v), (void*)P(o.out), P.mask, 1, o.batch, o.heads,
                                     o.nq, o.hd, o.ldq, o.ldk, o.ldv, o.ldo, o.scale, stream);
       break;
     default:
@@ -166,12 +147,12 @@ static int launch_op_f32(sdn_unet* u, const Op& o, const Operands& P, bool x3, f
 }
 
 // One op of a plan in the 16-bit storage modes (bf16, or f16 when `f16`).
-static int launch_op_16(sdn_unet* u, const Op& o, const Operands& P, bool f16, float timestep, const float* t_dev, void* stream) {
+static int launch_op_16(const sdn_unet* u, const Op& o, const Call& P, bool f16, const float* t_dev, void* stream) {
   int rc = SDN_OK;
   switch (o.kind) {
     case OP_TEMB:
       if (t_dev) rc = sdn_temb_from_device(f16 ? 1 : 0, t_dev, o.batch, o.c1, (void*)P(o.out), stream);
-      else rc = (f16 ? sdn_timestep_embed_f16 : sdn_timestep_embed_bf16)(timestep, o.batch, o.c1, (void*)P(o.out), stream);
+      else rc = (f16 ? sdn_timestep_embed_f16 : sdn_timestep_embed_bf16)(P.scalar, o.batch, o.c1, (void*)P(o.out), stream);
       break;
     case OP_CONV_IN:
       rc = (f16 ? sdn_conv_in_f16 : sdn_conv_in_bf16)((const float*)P(o.a), P(o.w), (const float*)P(o.bias), o.batch, o.c1, o.hw, o.hw, o.c2,
@@ -190,7 +171,7 @@ static int launch_op_16(sdn_unet* u, const Op& o, const Operands& P, bool f16, f
                              o.c1, o.c2, u->pcfg.eos_token_id, o.eps, (void*)P(o.out), nullptr, stream);
       break;
     case OP_COPY_ROWS:
-      rc = sdn_copy_rows_strided(P(o.a), o.batch, o.hw, o.c1, 2, (void*)P(o.out), u->proj_hbs, u->proj_hrs, stream);
+      rc = sdn_copy_rows_strided(P(o.a), o.batch, o.hw, o.c1, 2, (void*)P(o.out), P.out_bs, P.out_rs, stream);
       break;
     case OP_PATCH_ROWS:
       rc = sdn_clip_patch_rows(f16 ? 1 : 0, (const float*)P(o.a), o.batch, o.hw, o.patch, o.c1, (void*)P(o.out), stream);
@@ -205,7 +186,7 @@ static int launch_op_16(sdn_unet* u, const Op& o, const Operands& P, bool f16, f
       break;
     case OP_GEMM:
       if (o.dyn_ldc) {
-        sdn_gemm_desc gd = o.gd; gd.ldc = (int)u->proj_ers;
+        sdn_gemm_desc gd = o.gd; gd.ldc = (int)P.out2_rs;
         rc = (f16 ? sdn_gemm_f16 : sdn_gemm_bf16)(&gd, P(o.a), nullptr, P(o.w), nullptr, nullptr, nullptr, nullptr, (void*)P(o.out), stream);
         break;
       }
@@ -244,7 +225,7 @@ static int launch_op_16(sdn_unet* u, const Op& o, const Operands& P, bool f16, f
       rc = sdn_clip_embed(f16 ? 1 : 0, (const int32_t*)P(o.a), P(o.w), P(o.bias), o.rows, o.hw, o.c1, o.c2, (void*)P(o.out), stream);
       break;
     case OP_MATTN:
-      rc = sdn_masked_attention(f16 ? 1 : 0, P(o.a), P(o.k), P(o.v), (void*)P(o.out), (const int32_t*)u->clip_mask, 1, o.batch,
+      rc = sdn_masked_attention(f16 ? 1 : 0, P(o.a), P(o.k), P(o.v), (void*)P(o.out), P.mask, 1, o.batch,
                                 o.heads, o.nq, o.hd, o.ldq, o.ldk, o.ldv, o.ldo, o.scale, stream);
       break;
     case OP_RMSNORM:
@@ -257,7 +238,7 @@ static int launch_op_16(sdn_unet* u, const Op& o, const Operands& P, bool f16, f
       rc = sdn_t5_relative_bias(f16 ? 1 : 0, P(o.w), u->tcfg.num_buckets, u->tcfg.max_distance, o.heads, o.nq, (float*)P(o.out), stream);
       break;
     case OP_BATTN:
-      rc = sdn_bias_attention(f16 ? 1 : 0, P(o.a), P(o.k), P(o.v), (void*)P(o.out), (const float*)P(o.aux), (const int32_t*)u->clip_mask,
+      rc = sdn_bias_attention(f16 ? 1 : 0, P(o.a), P(o.k), P(o.v), (void*)P(o.out), (const float*)P(o.aux), P.mask,
                               o.batch, o.heads, o.nq, o.hd, o.ldq, o.ldk, o.ldv, o.ldo, o.scale, stream);
       break;
     case OP_REPEAT:
@@ -265,7 +246,7 @@ static int launch_op_16(sdn_unet* u, const Op& o, const Operands& P, bool f16, f
       break;
     case OP_LATENT_MIX:
       rc = sdn_latent_mix((const float*)P(o.a), (const float*)P(o.w), (const float*)P(o.bias), o.batch, o.c1, o.hw,
-                          o.mod ? o.scale : timestep /* decoder: the caller's latent_scale */,
+                          o.mod ? o.scale : P.scalar /* decoder: the caller's latent_scale */,
                           (float*)P(o.out), stream);
       break;
     case OP_SOFTMAX:
@@ -306,50 +287,43 @@ static int launch_op_16(sdn_unet* u, const Op& o, const Operands& P, bool f16, f
 }
 
 // Launches every op of the plan on `stream`.  t_dev != nullptr: the timestep is read from device memory (graph mode).
-static int launch_ops(sdn_unet* u, Plan* p, const char* W, const char* WS, const char* L, const char* T, const char* O,
-                      const char* PL, float timestep, const float* t_dev, bool prof, void* stream, bool skip_text_kv = false) {
-  const Operands P{W, WS, L, T, O, PL, WS + p->kv_base};
-  size_t opi = 0;
+static int launch_ops(sdn_unet* u, const Plan* p, const Call& c, const float* t_dev, bool prof, void* stream, bool skip_text_kv = false) {
   const int sdt = u->dtype();
   const bool f32 = sdt >= 2;                                                 // fp32-storage modes (SD-v1.4 UNet, CLIP and MMDiT plans)
-  for (const Op& o : p->ops) {
-    if (skip_text_kv && o.text_kv) { ++opi; continue; }       // its output of the previous forward stands (same text version)
-    if (o.kind == OP_COPY_ROWS && u->kind == CLIP_VISION && !u->vision_hidden) { ++opi; continue; }   // no last_hidden_state buffer was given
+  for (size_t opi = 0; opi < p->ops.size(); ++opi) {
+    const Op& o = p->ops[opi];
+    if ((skip_text_kv && o.text_kv) || (o.kind == OP_COPY_ROWS && !c.out)) continue;   // K / V of an unchanged text stand; no last_hidden_state buffer was given
     if (prof) (void)hipEventRecord(u->ev[2 * opi], (hipStream_t)stream);
-    const int rc = f32 ? launch_op_f32(u, o, P, sdt == 3, timestep, t_dev, stream) : launch_op_16(u, o, P, sdt == 1, timestep, t_dev, stream);
+    const int rc = f32 ? launch_op_f32(u, o, c, sdt == 3, t_dev, stream) : launch_op_16(u, o, c, sdt == 1, t_dev, stream);
     if (prof) (void)hipEventRecord(u->ev[2 * opi + 1], (hipStream_t)stream);
-    ++opi;
     if (rc != SDN_OK) return rc;
   }
   return SDN_OK;
 }
 
-int run_plan(sdn_unet* u, const void* weights, const float* latents, float timestep, const void* text,
-             const void* pooled, float* out, int32_t batch, void* workspace, size_t workspace_bytes, void* stream, int n) {
-  if (!u || !weights || !latents || !text || !out || !workspace || batch <= 0) return SDN_E_INVALID;
-  Plan* p = get_plan(u, batch, n);
+int run_plan(sdn_unet* u, const Call& given) {
+  if (!u || !given.weights || !given.workspace || given.batch <= 0) return SDN_E_INVALID;
+  Plan* p = get_plan(u, given.batch, given.n);
   if (p->ws_bytes < 0) return SDN_E_INVALID;                      // e.g. batch not a multiple of latent_repeat
-  if (workspace_bytes < (size_t)p->ws_bytes) return SDN_E_WORKSPACE;
-  const char* W = (const char*)weights; const char* WS = (const char*)workspace;
-  const char* L = (const char*)latents; const char* T = (const char*)text; const char* O = (const char*)out;
-  const char* PL = (const char*)pooled;
+  if (given.workspace_bytes < (size_t)p->ws_bytes) return SDN_E_WORKSPACE;
+  Call c = given; c.kv_base = p->kv_base;
   const bool prof = u->profile_next;
   if (prof) {                                    // opt-in diagnostics: HIP events around every launch of this forward
     u->profile_next = false;
     while (u->ev.size() < 2 * p->ops.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return SDN_E_LAUNCH; u->ev.push_back(e); }
-    u->profiled_batch = batch; u->profiled_n = n;
+    u->profiled_batch = c.batch; u->profiled_n = c.n;
   }
-  hipStream_t hs = (hipStream_t)stream;
+  hipStream_t hs = (hipStream_t)c.stream;
   if (u->use_graph && !prof && (u->kind == UNET || u->kind == MMDIT) && p->tscalar_off >= 0) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(hs, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
       // Graph mode: small batches are launch-bound (~850 launches per forward); the forward is captured once per
       // (batch, operand addresses) and replayed.  The timestep is the only per-step scalar: it is stored to the
       // workspace by one ordinary launch and k_temb reads it from there.
-      float* t_dev = (float*)(WS + p->tscalar_off);
-      int rc = sdn_set_scalar(t_dev, timestep, stream);
+      float* t_dev = (float*)((char*)c.workspace + p->tscalar_off);
+      int rc = sdn_set_scalar(t_dev, c.scalar, c.stream);
       if (rc != SDN_OK) return rc;
-      const sdn_unet::GraphKey key{batch, weights, latents, text, pooled, out, workspace};
+      const sdn_unet::GraphKey key{c.batch, c.weights, c.in, c.text, c.pooled, c.out, c.workspace};
       auto it = u->graphs.find(key);
       if (it == u->graphs.end()) {
         if (u->graphs.size() >= 16) {                          // operands keep moving: graphs do not pay, stop hoarding
@@ -360,7 +334,7 @@ int run_plan(sdn_unet* u, const void* weights, const float* latents, float times
         hipGraph_t graph = nullptr;
         if (!u->cap_stream && hipStreamCreateWithFlags(&u->cap_stream, hipStreamNonBlocking) != hipSuccess) return SDN_E_LAUNCH;
         if (hipStreamBeginCapture(u->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return SDN_E_LAUNCH;
-        rc = launch_ops(u, p, W, WS, L, T, O, PL, timestep, t_dev, false, (void*)u->cap_stream);   // records, does not run
+        rc = launch_ops(u, p, c, t_dev, false, (void*)u->cap_stream);   // records, does not run
         const hipError_t ec = hipStreamEndCapture(u->cap_stream, &graph);
         if (rc != SDN_OK || ec != hipSuccess || !graph) { if (graph) (void)hipGraphDestroy(graph); return rc != SDN_OK ? rc : SDN_E_LAUNCH; }
         hipGraphExec_t exec = nullptr;
@@ -373,13 +347,12 @@ int run_plan(sdn_unet* u, const void* weights, const float* latents, float times
       return hipGraphLaunch(it->second, hs) == hipSuccess ? SDN_OK : SDN_E_LAUNCH;
     }
   }
-  // text K / V reuse (ordinary launches only: a captured graph holds a fixed op list)
-  // (only UNet plans emit text_kv ops)
+  // text K / V reuse (ordinary launches only: a captured graph holds a fixed op list; only UNet plans emit text_kv ops)
   const bool declared = u->kind == UNET && u->text_version != 0 && u->subbatch_bytes == 0;
-  const bool skip = declared && !prof && u->kv_version == u->text_version && u->kv_batch == batch && u->kv_w == weights &&
-                    u->kv_text == text && u->kv_ws == workspace;
-  const int rc_l = launch_ops(u, p, W, WS, L, T, O, PL, timestep, nullptr, prof, stream, skip);
-  if (rc_l == SDN_OK && declared) { u->kv_version = u->text_version; u->kv_batch = batch; u->kv_w = weights; u->kv_text = text; u->kv_ws = workspace; }
+  const bool skip = declared && !prof && u->kv_version == u->text_version && u->kv_batch == c.batch && u->kv_w == c.weights &&
+                    u->kv_text == c.text && u->kv_ws == c.workspace;
+  const int rc_l = launch_ops(u, p, c, nullptr, prof, c.stream, skip);
+  if (rc_l == SDN_OK && declared) { u->kv_version = u->text_version; u->kv_batch = c.batch; u->kv_w = c.weights; u->kv_text = c.text; u->kv_ws = c.workspace; }
   else if (!declared) u->kv_version = 0;
   return rc_l;
 }
@@ -397,6 +370,11 @@ void drop_graphs(sdn_unet* u) {
 
 using namespace sdn_plan;
 
+// Milliseconds op i of the profiled forward took (between its two events); false when they cannot be read.
+static bool op_ms(const sdn_unet* u, size_t i, float* ms) {
+  return hipEventSynchronize(u->ev[2 * i + 1]) == hipSuccess && hipEventElapsedTime(ms, u->ev[2 * i], u->ev[2 * i + 1]) == hipSuccess;
+}
+
 // Undeclared debug hook (tools/profile_ops.py): per-launch rows of the profiled forward, in plan order.
 // out[i*6 + {0..5}] = {ms, flops, bytes, M, N, K}; labels[i*24..] = kernel label.  Returns the op count.
 extern "C" int sdn_debug_profile_ops(sdn_unet* u, double* out, char* labels, int max_ops) {
@@ -404,9 +382,8 @@ extern "C" int sdn_debug_profile_ops(sdn_unet* u, double* out, char* labels, int
   Plan* p = get_plan(u, u->profiled_batch, u->profiled_n);
   int n = 0;
   for (size_t i = 0; i < p->ops.size() && n < max_ops; ++i, ++n) {
-    if (hipEventSynchronize(u->ev[2 * i + 1]) != hipSuccess) return -2;
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, u->ev[2 * i], u->ev[2 * i + 1]) != hipSuccess) return -2;
+    if (!op_ms(u, i, &ms)) return -2;
     const Op& o = p->ops[i];
     out[n * 6 + 0] = ms; out[n * 6 + 1] = o.flops; out[n * 6 + 2] = o.bytes;
     out[n * 6 + 3] = o.kind == OP_GEMM ? o.gd.M : (o.kind == OP_ATTN ? o.nq : o.rows);
@@ -423,9 +400,8 @@ extern "C" int sdn_unet_profile_read(sdn_unet* u, sdn_profile_row* rows, int32_t
   if (u->ev.size() < 2 * p->ops.size()) return SDN_E_INVALID;
   int n = 0;
   for (size_t i = 0; i < p->ops.size(); ++i) {
-    if (hipEventSynchronize(u->ev[2 * i + 1]) != hipSuccess) return SDN_E_LAUNCH;
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, u->ev[2 * i], u->ev[2 * i + 1]) != hipSuccess) return SDN_E_LAUNCH;
+    if (!op_ms(u, i, &ms)) return SDN_E_LAUNCH;
     const Op& o = p->ops[i];
     int r = 0;
     for (; r < n; ++r) if (strcmp(rows[r].kernel, o.label) == 0) break;

@@ -18,7 +18,7 @@ void Builder::build_clip() {
   Ref tok = param("embeddings.token_embedding.weight", SDN_P_MAT, c.vocab_size, C);
   Ref pos = param("embeddings.position_embedding.weight", SDN_P_MAT, n, C);
   Act x = act(rows, C, n, 0);
-  { Op o; o.kind = OP_CLIP_EMBED; o.a = Ref{SP_LATENTS, 0}; o.w = tok; o.bias = pos; o.out = R(x); o.rows = rows; o.hw = n; o.c1 = C;
+  { Op o; o.kind = OP_CLIP_EMBED; o.a = Ref{SP_IN, 0}; o.w = tok; o.bias = pos; o.out = R(x); o.rows = rows; o.hw = n; o.c1 = C;
     o.c2 = c.vocab_size; o.bytes = 6.0 * rows * C; snprintf(o.label, sizeof(o.label), "k_clip_embed"); plan->ops.push_back(o); }
   const bool proj = u->kind == CLIP_PROJ;
   const int mlp_act = proj ? u->pcfg.act : SDN_ACT_QUICK_GELU;
@@ -66,11 +66,11 @@ void Builder::build_clip() {
     const int P = u->pcfg.projection_dim;
     Ref tpw = param("text_projection.weight", SDN_P_MAT, P, C);
     Act pooled = act(B, C, 1, 0);
-    { Op o; o.kind = OP_EOS_ROWS; o.a = Ref{SP_LATENTS, 0}; o.k = R(x); o.w = fg; o.bias = fb; o.out = R(pooled); o.batch = B; o.hw = n;
+    { Op o; o.kind = OP_EOS_ROWS; o.a = Ref{SP_IN, 0}; o.k = R(x); o.w = fg; o.bias = fb; o.out = R(pooled); o.batch = B; o.hw = n;
       o.c1 = C; o.c2 = c.vocab_size; o.eps = 1e-5f; o.bytes = 2.0 * es * B * C + 4.0 * rows;
       snprintf(o.label, sizeof(o.label), "k_clip_eos_rows"); plan->ops.push_back(o); }
     drop(x);
-    gemm(B, P, C, R(pooled), tpw, Ref(), Ref{SP_POOLED, 0});
+    gemm(B, P, C, R(pooled), tpw, Ref(), Ref{SP_OUT2, 0});
     plan->ops.back().dyn_ldc = 1;
     drop(pooled);
     plan->ws_bytes = arena.peak;
@@ -124,7 +124,7 @@ void Builder::build_t5() {
   const int64_t rows = (int64_t)B * n;
   Ref tok = param("embed_tokens.weight", SDN_P_MAT, c.vocab_size, D);
   Act x = act(rows, D, n, 0, 4);
-  { Op o; o.kind = OP_EMBED; o.a = Ref{SP_LATENTS, 0}; o.w = tok; o.out = R(x); o.rows = rows; o.c1 = D; o.c2 = c.vocab_size;
+  { Op o; o.kind = OP_EMBED; o.a = Ref{SP_IN, 0}; o.w = tok; o.out = R(x); o.rows = rows; o.c1 = D; o.c2 = c.vocab_size;
     o.bytes = 6.0 * rows * D; snprintf(o.label, sizeof(o.label), "k_embed_tokens"); plan->ops.push_back(o); }
   Act bias = act(H, 2 * n - 1, 0, 0, 4);               // computed once per forward, shared by every layer
   char buf[96];

@@ -348,7 +348,7 @@ void Builder::build() {
   if (B % rep != 0) { plan->ws_bytes = -1; return; }            // forward rejects this batch
   const int Bfull = B, Bp = B / rep;
   Act hp = act((int64_t)Bp * S * S, ch0, S * S, S);
-  { Op o; o.kind = OP_CONV_IN; o.batch = Bp; o.c1 = c.in_channels; o.c2 = ch0; o.hw = S; o.a = Ref{SP_LATENTS, 0}; o.w = ciw; o.bias = cib; o.out = R(hp);
+  { Op o; o.kind = OP_CONV_IN; o.batch = Bp; o.c1 = c.in_channels; o.c2 = ch0; o.hw = S; o.a = Ref{SP_IN, 0}; o.w = ciw; o.bias = cib; o.out = R(hp);
     o.flops = 2.0 * Bp * S * S * (double)ch0 * 9 * c.in_channels; o.bytes = (double)Bp * S * S * (4.0 * c.in_channels + 2.0 * ch0);
     snprintf(o.label, sizeof(o.label), "k_conv_in"); plan->ops.push_back(o);
     plan->flops += o.flops; }

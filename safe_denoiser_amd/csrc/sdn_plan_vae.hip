@@ -113,7 +113,7 @@ void Builder::build_vae() {
   gn_stats = Ref{SP_WS, arena.alloc((int64_t)B * 129 * 64 * 2 * 4)};
   Ref pqw = param("post_quant_conv.weight", SDN_P_VEC_F32, L * L, 0), pqb = param("post_quant_conv.bias", SDN_P_VEC_F32, L, 0);
   Act z = act((int64_t)B * L, S * S, 0, 0, 4);                    // fp32 NCHW
-  { Op o; o.kind = OP_LATENT_MIX; o.batch = B; o.c1 = L; o.hw = S * S; o.a = Ref{SP_LATENTS, 0}; o.w = pqw; o.bias = pqb; o.out = R(z);
+  { Op o; o.kind = OP_LATENT_MIX; o.batch = B; o.c1 = L; o.hw = S * S; o.a = Ref{SP_IN, 0}; o.w = pqw; o.bias = pqb; o.out = R(z);
     o.flops = 2.0 * B * S * S * (double)L * L; o.bytes = 8.0 * B * S * S * L; snprintf(o.label, sizeof(o.label), "k_latent_mix");
     plan->ops.push_back(o); plan->flops += o.flops; }
   Ref ciw = param("decoder.conv_in.weight", SDN_P_CONV3X3, ctop, 9 * L), cib = param("decoder.conv_in.bias", SDN_P_VEC_F32, ctop, 0);
@@ -167,7 +167,7 @@ void Builder::build_vae_encoder() {
   const int c0 = c.block_out_channels[0];
   Ref ciw = param("encoder.conv_in.weight", SDN_P_CONV3X3, c0, 9 * c.out_channels), cib = param("encoder.conv_in.bias", SDN_P_VEC_F32, c0, 0);
   Act cur = act((int64_t)B * S0 * S0, c0, S0 * S0, S0);
-  { Op o; o.kind = OP_CONV_IN; o.batch = B; o.c1 = c.out_channels; o.c2 = c0; o.hw = S0; o.a = Ref{SP_LATENTS, 0}; o.w = ciw; o.bias = cib; o.out = R(cur);
+  { Op o; o.kind = OP_CONV_IN; o.batch = B; o.c1 = c.out_channels; o.c2 = c0; o.hw = S0; o.a = Ref{SP_IN, 0}; o.w = ciw; o.bias = cib; o.out = R(cur);
     o.flops = 2.0 * B * S0 * S0 * (double)c0 * 9 * c.out_channels; o.bytes = (double)B * S0 * S0 * (4.0 * c.out_channels + 2.0 * c0);
     snprintf(o.label, sizeof(o.label), "k_conv_in"); plan->ops.push_back(o); plan->flops += o.flops; }
   for (int i = 0; i < n; ++i) {

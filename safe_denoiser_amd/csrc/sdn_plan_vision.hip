@@ -22,7 +22,7 @@ void Builder::build_clip_vision() {
   Ref pos = param("embeddings.position_embedding.weight", SDN_P_MAT, n, C);
   Ref pg = param("pre_layrnorm.weight", SDN_P_VEC_F32, C, 0), pb = param("pre_layrnorm.bias", SDN_P_VEC_F32, C, 0);
   Act pr = act(prows, Kpad, P, 0);
-  { Op o; o.kind = OP_PATCH_ROWS; o.a = Ref{SP_LATENTS, 0}; o.out = R(pr); o.batch = B; o.hw = c.image_size; o.patch = c.patch_size;
+  { Op o; o.kind = OP_PATCH_ROWS; o.a = Ref{SP_IN, 0}; o.out = R(pr); o.batch = B; o.hw = c.image_size; o.patch = c.patch_size;
     o.c1 = Kpad; o.rows = prows; o.bytes = 12.0 * B * c.image_size * c.image_size + 2.0 * prows * Kpad;
     snprintf(o.label, sizeof(o.label), "k_clip_patch_rows"); plan->ops.push_back(o); }
   Act pp = act(prows, C, P, 0);
@@ -75,7 +75,7 @@ void Builder::build_clip_vision() {
   { Op o; o.kind = OP_CLASS_ROWS; o.a = R(x); o.w = qg; o.bias = qb; o.out = R(pooled); o.batch = B; o.hw = n; o.c1 = C; o.eps = 1e-5f;
     o.rows = B; o.bytes = 2.0 * es * B * C; snprintf(o.label, sizeof(o.label), "k_clip_class_rows"); plan->ops.push_back(o); }
   drop(x);
-  gemm(B, c.projection_dim, C, R(pooled), vpw, Ref(), Ref{SP_POOLED, 0});
+  gemm(B, c.projection_dim, C, R(pooled), vpw, Ref(), Ref{SP_OUT2, 0});
   drop(pooled);
   plan->ws_bytes = arena.peak;
 }
@@ -104,15 +104,14 @@ extern "C" int sdn_clip_vision_create(const sdn_clip_vision_config* cfg, sdn_une
 
 extern "C" int sdn_clip_vision_forward(sdn_unet* m, const void* weights, const float* pixel_values, void* last_hidden_state,
                                        void* image_embeds, int32_t batch, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!m || m->kind != CLIP_VISION || !image_embeds || !workspace) return SDN_E_INVALID;
+  if (!m || m->kind != CLIP_VISION || !pixel_values || !image_embeds) return SDN_E_INVALID;
   if ((reinterpret_cast<uintptr_t>(pixel_values) & 15) || (reinterpret_cast<uintptr_t>(last_hidden_state) & 15) ||
       (reinterpret_cast<uintptr_t>(image_embeds) & 15))
     return SDN_E_INVALID;
   const sdn_clip_vision_config& c = m->vis;
   const int g = c.image_size / c.patch_size, n = 1 + g * g;
-  m->vision_hidden = last_hidden_state != nullptr;
-  m->proj_hbs = (int64_t)n * c.hidden_size; m->proj_hrs = c.hidden_size;      // the copy's destination is contiguous
-  // (without a last_hidden_state buffer nothing resolves an SP_OUT reference: the plan runner only wants the pointer non-null)
-  return run_plan(m, weights, pixel_values, 0.f, weights /* no text operand */, image_embeds,
-                  (float*)(last_hidden_state ? last_hidden_state : workspace), batch, workspace, workspace_bytes, stream);
+  Call call(weights, workspace, workspace_bytes, batch, stream);
+  call.in = pixel_values; call.out = last_hidden_state; call.out2 = image_embeds;   // out is nullable: the copy into it is skipped
+  call.out_bs = (int64_t)n * c.hidden_size; call.out_rs = c.hidden_size;            // the copy's destination is contiguous
+  return run_plan(m, call);
 }

@@ -56,6 +56,19 @@ def test_fp32_storage_modes_match_transformers_golden_case(precision, tol):
         CLIPTextModel(precision="fp8", **cfg)
 
 
+def test_key_padding_mask_does_not_outlive_its_forward():
+    """One handle runs a forward with a key-padding mask (keys masked in every row), then one without: the second equals a fresh
+    handle's unmasked forward on the same ids, bit for bit."""
+    sd, cfg, ids, *_ = load_gold()
+    ids = ids[:2].cuda()
+    mask = (torch.arange(77)[None, :] < torch.tensor([[20], [50]])).long().cuda()
+    m, fresh = CLIPTextModel(**cfg), CLIPTextModel(**cfg)
+    m.load_state_dict(sd); fresh.load_state_dict(sd)
+    want = fresh(ids)[0]
+    assert not torch.equal(m(ids, attention_mask=mask)[0], want)          # the mask is not a no-op on these rows
+    assert torch.equal(m(ids)[0], want)
+
+
 def test_masked_attention_f32_against_torch():
     """sdn_masked_attention_f32 alone: causal, key-padding, and both, on strided q / k / v (the stacked qkv buffer's layout)."""
     import safe_denoiser_amd as sda

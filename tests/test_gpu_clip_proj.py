@@ -288,6 +288,27 @@ def test_strided_outputs_equal_cat_and_pad(tag):
         ea.forward_into(ids_a, hview[:, :77, off:off + 128], eview[:, :64])       # a slice that starts off a 16-byte boundary
 
 
+def test_output_strides_do_not_outlive_their_forward():
+    """One handle writes into padded slices (row strides 256 / 192 of sentinel-filled buffers), then into contiguous tensors: the second
+    call writes exactly the contiguous layout and equals a fresh handle's result, and the first call's padding keeps its sentinels."""
+    m, fresh = small("a", DT["f16"]), small("a", DT["f16"])
+    ids = gold("a", "ids")[:2]
+    want = fresh(ids)
+    hb, hview = X.guarded_like((2, 80, 256), DT["f16"], "cuda")
+    eb, eview = X.guarded_like((2, 192), DT["f16"], "cuda")
+    hview.fill_(-7.0); eview.fill_(-7.0)
+    m.forward_into(ids, hview[:, :77, :128], eview[:, :64])
+    hc, hcv = X.guarded_like((2, 77, 128), DT["f16"], "cuda")
+    ec, ecv = X.guarded_like((2, 64), DT["f16"], "cuda")
+    m.forward_into(ids, hcv, ecv)
+    torch.cuda.synchronize()
+    assert torch.equal(hcv, want.hidden_states[-2]) and torch.equal(ecv, want.text_embeds)
+    assert X.sentinels_intact(hc, hcv) == 0 and X.sentinels_intact(ec, ecv) == 0
+    assert torch.equal(hview[:, :77, :128], want.hidden_states[-2]) and torch.equal(eview[:, :64], want.text_embeds)
+    assert torch.all(hview[:, 77:] == -7.0) and torch.all(hview[:, :77, 128:] == -7.0) and torch.all(eview[:, 64:] == -7.0)
+    assert X.sentinels_intact(hb, hview) == 0 and X.sentinels_intact(eb, eview) == 0
+
+
 # ---------------------------------------------------------------------------------------------- 5. full size
 def device_state_dict(m, seed):
     g = torch.Generator(device="cuda").manual_seed(seed)

@@ -78,6 +78,25 @@ def test_engine_matches_the_transformers_fixture(tag):
     assert lean.last_hidden_state is None and torch.equal(lean.image_embeds, e)
 
 
+def test_hidden_state_buffer_given_then_withheld_then_given_again():
+    """One handle through the C interface: a forward with a last_hidden_state buffer, one without, one with again, every output buffer
+    filled with NaN beforehand.  image_embeds are identical across the three and the third hidden state equals the first.  (Without
+    a buffer nothing in the plan names the hidden-state operand, so there is no substitute address whose bytes could be checked.)"""
+    m = small(torch.float16)
+    pv = gold("pixel_values")[:2].cuda().contiguous()
+    ws = m._workspace(2, pv.device)
+    hid = [torch.full((2, 17, 128), float("nan"), dtype=torch.float16, device="cuda") for _ in range(2)]
+    emb = [torch.full((2, 64), float("nan"), dtype=torch.float16, device="cuda") for _ in range(3)]
+    for e, h in zip(emb, (hid[0], None, hid[1])):
+        assert sda.lib().sdn_clip_vision_forward(m._h, m._weights.data_ptr(), pv.data_ptr(), None if h is None else h.data_ptr(), e.data_ptr(),
+                                                 2, ws.data_ptr(), ws.numel(), _lib.stream_ptr()) == 0
+    torch.cuda.synchronize()
+    assert torch.isfinite(emb[0].float()).all() and torch.isfinite(hid[0].float()).all()
+    assert torch.equal(emb[1], emb[0]) and torch.equal(emb[2], emb[0]) and torch.equal(hid[1], hid[0])
+    want = m(pv)
+    assert torch.equal(want.image_embeds, emb[0]) and torch.equal(want.last_hidden_state, hid[0])
+
+
 # ---------------------------------------------------------------------------------------------- 2. preprocessing
 def _images(size, n=2, seed=0):
     rng = np.random.default_rng(seed + size)

@@ -293,6 +293,17 @@ def test_short_sequence_equals_its_padded_and_masked_form(tag):
     assert ea <= bound and eb <= bound and O.rel_l2(a, b) <= bound
 
 
+def test_key_padding_mask_does_not_outlive_its_forward():
+    """One handle runs a forward with a key-padding mask (keys masked in every row), then one without: the second equals a fresh
+    handle's unmasked forward on the same ids, bit for bit.  n = 8, batch 2."""
+    ids = torch.from_numpy(G["ids"])[:2, :8]
+    mask = (torch.arange(8)[None] < torch.tensor([[5], [3]])).long()
+    m, fresh = small(DT["bf16"]), small(DT["bf16"])
+    want = fresh(ids)[0]
+    assert not torch.equal(m(ids, attention_mask=mask)[0], want)          # the mask is not a no-op on these rows
+    assert torch.equal(m(ids)[0], want)
+
+
 # ---------------------------------------------------------------------------------------------- 5. full width
 XXL4 = dict(num_layers=4)
 

@@ -1,7 +1,7 @@
 """Fingerprint of everything the host-side planner decides, for checking that a change to csrc/sdn_plan*.hip leaves the plans alone.
 
 For a fixed list of handles (the configurations the host tests create: full-size and small UNet, MMDiT, VAE decoder / encoder, CLIP,
-projected CLIP and T5, at every storage dtype their creators accept) it prints one line per (handle, toggle, batch): parameter count,
+projected CLIP, T5 and the CLIP vision tower, at every storage dtype their creators accept) it prints one line per (handle, toggle, batch): parameter count,
 SHA-256 over every sdn_param_info, weight bytes, workspace bytes, FLOPs and their attention share.  The arena's peak depends on the
 order of every allocation and release and the FLOP sums cover every op, so a moved, dropped or reordered emitter call shows up.
 Host only: no GPU is touched.  Compare two builds by running each in a process of its own and diffing the outputs:
@@ -17,6 +17,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from safe_denoiser_amd import _lib  # noqa: E402
 from safe_denoiser_amd.clip import ACT_CODES, SD3_CLIP_G_CONFIG, SD3_CLIP_L_CONFIG, SD14_CLIP_CONFIG  # noqa: E402
+from safe_denoiser_amd.clip_vision import VIT_L14_CONFIG  # noqa: E402
 from safe_denoiser_amd.mmdit import SD3_MEDIUM  # noqa: E402
 from safe_denoiser_amd.t5 import T5_XXL_CONFIG  # noqa: E402
 from safe_denoiser_amd.unet import SD14_CONFIG  # noqa: E402
@@ -85,12 +86,21 @@ def t5_cfg(dtype, **kw):
                          max_distance=c["relative_attention_max_distance"], eps=c["layer_norm_epsilon"], dtype=dtype)
 
 
+def clip_vision_cfg(dtype, **kw):
+    c = dict(VIT_L14_CONFIG, **kw)
+    return _lib.ClipVisionConfig(image_size=c["image_size"], patch_size=c["patch_size"], hidden_size=c["hidden_size"],
+                                 intermediate_size=c["intermediate_size"], num_layers=c["num_hidden_layers"],
+                                 num_heads=c["num_attention_heads"], projection_dim=c["projection_dim"], act=ACT_CODES[c["hidden_act"]],
+                                 dtype=dtype)
+
+
 SMALL_UNET = dict(block_out_channels=(64, 64), down_block_types=("CrossAttnDownBlock2D", "DownBlock2D"), layers_per_block=1,
                   attention_head_dim=1, cross_attention_dim=64, sample_size=8, norm_num_groups=32)
 SMALL_MMDIT = dict(sample_size=16, num_layers=3, num_attention_heads=4, joint_attention_dim=128, pooled_projection_dim=64)
 SMALL_VAE = dict(block_out_channels=(64, 128), layers_per_block=1, sample_size=16)
 SMALL_CLIP = dict(vocab_size=128, hidden_size=128, intermediate_size=128, num_hidden_layers=2, num_attention_heads=2)
 SMALL_T5 = dict(vocab_size=512, d_model=128, d_ff=256, num_layers=2, num_heads=2)
+SMALL_VISION = dict(image_size=56, hidden_size=128, intermediate_size=128, num_hidden_layers=2, num_attention_heads=2, projection_dim=64)
 
 
 def handles():
@@ -113,6 +123,8 @@ def handles():
                 range(4), "other"))
     out.append(("t5/xxl", "sdn_t5_create", lambda d: t5_cfg(d), range(2), "t5"))
     out.append(("t5/small", "sdn_t5_create", lambda d: t5_cfg(d, **SMALL_T5), range(2), "t5"))
+    out.append(("clip_vision/L14", "sdn_clip_vision_create", lambda d: clip_vision_cfg(d), range(2), "other"))
+    out.append(("clip_vision/small", "sdn_clip_vision_create", lambda d: clip_vision_cfg(d, **SMALL_VISION), range(2), "other"))
     return out
 
 
