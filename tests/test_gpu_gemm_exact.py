@@ -11,7 +11,6 @@ import os
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 import safe_denoiser_amd as sda
 from tests_support import exact as X
@@ -34,45 +33,7 @@ def _t(g, *shape, scale=1.0, dt=torch.bfloat16):
     return (torch.randn(*shape, generator=g) * scale).to(dt).cuda()
 
 
-def _im2col(x, conv):
-    """NHWC 16-bit map -> float64 [B * Ho * Wo, Cin * 9] (channel-major taps, F.unfold order) of the conv the kernel runs."""
-    xc = x.to(F64).permute(0, 3, 1, 2)
-    if conv.get("upsample"):
-        xc = xc.repeat_interleave(2, 2).repeat_interleave(2, 3)
-    xc = F.pad(xc, (0, 1, 0, 1) if conv.get("asym_pad") else (1, 1, 1, 1))
-    cols = F.unfold(xc, 3, stride=conv.get("stride", 1))
-    return cols.transpose(1, 2).reshape(-1, cols.shape[1])
-
-
-def _reference(a, w, *, a2=None, conv=None, bias=None, rowbias=None, rowgate=None, residual=None, residual_bcast=0, rpb=0, act=0):
-    """(y, S', E_epi, y32): exact float64 result, its magnitude, the activation's documented error, and plain fp32 arithmetic
-    on the same operands (tf32 off) for the exact-rounding-rate baseline."""
-    if conv:
-        A = _im2col(a, conv)
-        N = w.shape[0]
-        W = w.to(F64).view(N, 3, 3, -1).permute(0, 3, 1, 2).reshape(N, -1)
-    else:
-        A = a.to(F64) if a2 is None else torch.cat([a.to(F64), a2.to(F64)], 1)
-        W = w.to(F64)
-    M = A.shape[0]
-    y, s = A @ W.T, A.abs() @ W.abs().T + X.subnormal_term(A, W, w.dtype) / X.ACC      # (E_sub rides in S' through the epilogue)
-    y32 = A.float() @ W.float().T
-    b_of = torch.arange(M, device=A.device) // rpb if rpb else None
-    if bias is not None:
-        y, s, y32 = y + bias.to(F64), s + bias.to(F64).abs(), y32 + bias
-    if rowbias is not None:
-        rb = rowbias[b_of]
-        y, s, y32 = y + rb.to(F64), s + rb.to(F64).abs(), y32 + rb
-    if rowgate is not None:
-        gt = rowgate[b_of]
-        y, s, y32 = y * gt.to(F64), s * gt.to(F64).abs(), y32 * gt
-    if residual is not None:
-        r = residual[torch.arange(M, device=A.device) % rpb] if residual_bcast else residual
-        y, s, y32 = y + r.to(F64), s + r.to(F64).abs(), y32 + r.float()
-    y, s, e = X.apply_act(y, s, act)
-    if act == 1:
-        y32 = F.silu(y32)
-    return y, s, e, (y32 if act in (0, 1) else None)
+_im2col, _reference = X.im2col, X.reference       # (shared with tests/test_gpu_x3_exact.py)
 
 
 def _check(name, dt, key, out, buf, y, s, e, y32, *, exact_fn, out_dtype=None, direction=True):
@@ -283,15 +244,7 @@ def _no_tf32():
     torch.backends.cuda.matmul.allow_tf32 = prev
 
 
-def _run_all(fn, dt, cases):
-    """Runs every case (a failure does not hide the cases after it), then reports all failures at once."""
-    errs = []
-    for name, (key, kw) in cases.items():
-        try:
-            fn(name, dt, key, **kw)
-        except AssertionError as e:
-            errs.append(str(e).split("\n")[0])
-    assert not errs, "\n".join(errs)
+_run_all = X.run_all
 
 
 @pytest.mark.parametrize("dt", DTYPES, ids=["bf16", "f16"])

@@ -45,10 +45,42 @@ Also, per case:
 
 Guard bands: outputs are views into larger buffers filled with a NaN bit pattern (before, after and in the ldc gap); the
 pattern must survive bit for bit.  Inputs carry NaN rows past their valid extent, so a stray read poisons a checked value.
+
+fp32-storage GEMM forms (the contractions of the precise plans; tests/test_gpu_x3_exact.py).  The bf16x3 product is a defined
+function of the split operands, so the kernels are held to ACCUMULATION error, not to the 2^-16 of the scheme:
+
+    |out - y3| <= 1/2 ulp_f32(y3) + X3_ACC[family] * S3 + E_epi
+
+  x3t   triple-operand path (sdn_gemm_bf16 with x3_out over [hi | lo | hi] rows and [hi | hi | lo] weights, K' = 3K): the kernel's
+        inputs ARE the bf16 triples (ops.split3 / ops.expand3), y3 = A3 . W3^T in float64 over those values, S3 = |A3| . |W3|^T
+        (+ |bias| + |rowbias| + |residual|).
+  x3    sdn_gemm_x3 (k_gemm_x3: operands split in the kernel): hi = RNE_bf16(x), lo = RNE_bf16(x - hi) reproduced on the host
+        (x3_operands), y3 = Ahi Whi^T + Alo Whi^T + Ahi Wlo^T, S3 the same three terms of absolute values.
+  f32   sdn_gemm_f32 (k_gemm_f32, also the M < 64 fallback of the x3 entry): y = A . W^T of the f32 operands, S = |A| . |W|^T.
+  E_epi SiLU / tanh-GELU as above (ACT_REL |x|); GEGLU on these paths evaluates an erf (erff, or Abramowitz-Stegun 7.1.26 with
+        |error| <= 1.5e-7), not the quintic: E_epi = ACT_REL |h|, no 2.6e-5 term.
+  Triple (x3_out 3) and pair (x3_out 4) outputs: bit equality with the split of the checked f32-row result (x3_out 1) of the same
+        operands -- hi == bf16(f), lo == bf16(f - hi), third plane == hi.  The GEGLU triple (x3_out 2) has no f32-row form on that
+        path: hi + lo is held to ACC S' + E_epi + 2^-16 |y| (PAIR_REL: what a hi | lo pair can carry) and its two hi planes to
+        bit equality.
+  X3_ACC  starts from ACC = 2^-20, which was measured on 16-bit chains; the derivable hard bound of a K'-term fp32 chain is
+        K' 2^-24 S (2^-16.4 at K' = 192, 2^-13.2 at the slab case's K' = 1728).  Measured on MI355X, normal operands
+        (profiles/x3_exact.json, log2_err_over_S per case; worst per family): k_gemm_x3 2^-22.4 S3 (K' = 192 ... 1728), k_gemm_f32's f32-input MFMA 2^-21.7 S (K = 64 ... 576),
+        the triple path 2^-21.0 S3 on the plain tiles (K' = 192 ... 1728) and 2^-20.7 S3 on the slab ring at K' = 1728 (15.7 M
+        elements; 0.6 of the whole bound there, the closest any case comes).  No family exceeds 2^-20 S, so all three keep
+        X3_ACC = ACC = 2^-20 unchanged: a margin of 5.3x / 3.3x / 1.6x over the measured worst (2^-20 is 1/12 of
+        the hard bound at K' = 192, 1/110 at K' = 1728).  (The GEGLU triple's hi + lo sits at 2^-19.1 S': that is the 2^-16 |y| of the pair, not accumulation.)  A
+        family that comes to need more gets its own constant of 4x its measured worst, below K' 2^-24, stated here with the
+        measurement; a value above the hard bound is a bug to find.
+  The scheme itself, |y3 - y| <= 3 * 2^-16 S (SCHEME_REL), is pinned on the CPU (tests/test_exact_checker.py); the operator-level
+  3e-5 rel-L2 bounds of tests/test_gpu_f32.py and tests/test_gpu_x3t.py rest on it.
+  Clamped loads: k_gemm_x3 fetches rows past M / N from the last valid row instead of predicating, so its A and W operands live
+  in exact-size allocations bracketed by NaN rows (bracketed): one row past the clamp poisons a checked value.
 """
 import math
 
 import torch
+import torch.nn.functional as F
 
 ACC = 2.0 ** -20
 GELU_D = 1.13                  # max |d/dx| of GELU (erf or tanh form) and SiLU (1.0998)
@@ -98,8 +130,9 @@ def subnormal_term(A: torch.Tensor, W: torch.Tensor, dtype) -> torch.Tensor:
     return SUBNORMAL_ABS * torch.clamp(sub(A)[:, None] + sub(W)[None, :], max=1.0)
 
 
-def apply_act(y, s, act):
-    """Exact activation of the float64 pre-activation y with magnitude s: (value, S', E_epi).  act codes as sdn_gemm_desc."""
+def apply_act(y, s, act, exact_gelu=False):
+    """Exact activation of the float64 pre-activation y with magnitude s: (value, S', E_epi).  act codes as sdn_gemm_desc.
+    exact_gelu: the GEGLU gate is evaluated with an erf (the fp32-storage paths), not the quintic: E_epi = ACT_REL |h|."""
     zero = torch.zeros_like(y)
     if act == 0:
         return y, s, zero
@@ -114,18 +147,20 @@ def apply_act(y, s, act):
         gg = gelu64(g)
         v = (h * gg).reshape(M, N // 2)
         sp = (sh * gg.abs() + GELU_D * h.abs() * sg).reshape(M, N // 2)
-        return v, sp, (GEGLU_ABS * h.abs()).reshape(M, N // 2)
+        return v, sp, ((ACT_REL if exact_gelu else GEGLU_ABS) * h.abs()).reshape(M, N // 2)
     raise ValueError(act)
 
 
-def analyse(out: torch.Tensor, y: torch.Tensor, s: torch.Tensor, e_epi=None, dtype=None) -> dict:
-    """Statistics of out (any float dtype, the kernel's output) against the exact y (float64) with magnitude s."""
+def analyse(out: torch.Tensor, y: torch.Tensor, s: torch.Tensor, e_epi=None, dtype=None, acc=None) -> dict:
+    """Statistics of out (any float dtype, the kernel's output) against the exact y (float64) with magnitude s.
+    acc: the accumulation constant per unit of S' (default ACC; the fp32-storage families pass theirs, X3_ACC)."""
+    acc = ACC if acc is None else acc
     dtype = dtype or out.dtype
     o = out.to(torch.float64)
     y = y.to(torch.float64)
     u = ulp(y, dtype)
     rn = round_to(y, dtype)
-    tol = 0.5 * u + ACC * s + (0 if e_epi is None else e_epi)
+    tol = 0.5 * u + acc * s + (0 if e_epi is None else e_epi)
     fin_rn = torch.isfinite(rn)
     nan = torch.isnan(o)
     # overflow: required where y shrunk by the non-rounding budget still rounds to inf, allowed where y grown by it does
@@ -206,6 +241,16 @@ def guarded(rows: int, width: int, dtype, device, *, ldc=None, pad=256):
     return buf, buf[pad:pad + rows * ldc].view(rows, ldc)[:, :width]
 
 
+def guarded_planes(rows: int, planes: int, width: int, dtype, device, *, ldc=None, pad=256):
+    """(buffer, view): view [rows, planes, width] of rows made of `planes` planes of ldc (>= width) elements each -- the bf16
+    hi | lo | hi triples (3 planes) and hi | lo pairs (2) of the bf16x3 plan -- inside a sentinel buffer: guards before, after and
+    in every plane's ldc gap."""
+    ldc = ldc or width
+    n = rows * planes * ldc
+    buf = sentinel_fill(torch.empty(2 * pad + n, dtype=dtype, device=device))
+    return buf, buf[pad:pad + n].view(rows, planes, ldc)[:, :, :width]
+
+
 def guarded_like(shape, dtype, device, pad=256):
     """(buffer, view) of a contiguous tensor of `shape` between two sentinel bands."""
     n = math.prod(shape)
@@ -220,6 +265,24 @@ def sentinels_intact(buf: torch.Tensor, view: torch.Tensor) -> int:
     inside = torch.zeros(buf.numel(), dtype=torch.bool, device=buf.device)
     inside[idx.as_strided(view.shape, view.stride(), off).flatten()] = True
     return int((_int_view(buf)[~inside] != _sent_value(buf.dtype)).sum())
+
+
+def bracketed(t: torch.Tensor, rows: int = 8) -> torch.Tensor:
+    """Copy of t [R, ...] in an allocation of rows + R + rows rows whose first and last `rows` rows are NaN; returns the [R, ...]
+    view.  For operands a kernel fetches with CLAMPED row indices (k_gemm_x3: a row past the end legitimately re-reads the last
+    valid row, so zero-fill guard rows say nothing): one row past the clamp, either side, poisons a checked value."""
+    buf = torch.full((t.shape[0] + 2 * rows,) + tuple(t.shape[1:]), float("nan"), dtype=t.dtype, device=t.device)
+    buf[rows:rows + t.shape[0]] = t
+    return buf[rows:rows + t.shape[0]]
+
+
+def nan_strided(t: torch.Tensor, ld: int, extra_rows: int = 64) -> torch.Tensor:
+    """Copy of t [R, W] as a view with row stride ld >= W inside a NaN allocation of R + extra_rows rows (a residual that shares
+    the output's ldc): the gap columns and the rows past R are NaN."""
+    R, W = t.shape
+    buf = torch.full((R + extra_rows, ld), float("nan"), dtype=t.dtype, device=t.device)
+    buf[:R, :W] = t
+    return buf[:R, :W]
 
 
 def with_nan_tail(t: torch.Tensor, extra_rows: int) -> torch.Tensor:
@@ -245,3 +308,118 @@ def launch_key(rec) -> tuple:
     """sdn_debug_gemm_last_launch's record -> the INSTANTIATIONS key it ran."""
     fam = FAMILY[rec[0]]
     return ("dma",) + tuple(rec[2:6]) if fam == "dma" else (fam,)
+
+
+# ---- float64 references shared by the element-exact GPU tests ---------------------------------------------------------------------
+F64 = torch.float64
+
+
+def im2col(x, conv):
+    """NHWC map -> float64 [B * Ho * Wo, Cin * 9] (channel-major taps, F.unfold order) of the conv the kernel runs."""
+    xc = x.to(F64).permute(0, 3, 1, 2)
+    if conv.get("upsample"):
+        xc = xc.repeat_interleave(2, 2).repeat_interleave(2, 3)
+    xc = F.pad(xc, (0, 1, 0, 1) if conv.get("asym_pad") else (1, 1, 1, 1))
+    cols = F.unfold(xc, 3, stride=conv.get("stride", 1))
+    return cols.transpose(1, 2).reshape(-1, cols.shape[1])
+
+
+def operands(a, w, *, a2=None, conv=None):
+    """(A [M, K], W [N, K]) in float64: the matrices of the contraction a GEMM-family call runs (im2col of an NHWC map with the
+    weight's taps reordered to match, or the two sources side by side)."""
+    if conv:
+        N = w.shape[0]
+        return im2col(a, conv), w.to(F64).view(N, 3, 3, -1).permute(0, 3, 1, 2).reshape(N, -1)
+    return (a.to(F64) if a2 is None else torch.cat([a.to(F64), a2.to(F64)], 1)), w.to(F64)
+
+
+def split_bf16(x):
+    """The in-kernel bf16x3 split of float64-held f32 values: hi = RNE_bf16(x), lo = RNE_bf16(x - hi), both as float64."""
+    x32 = x.float()
+    hi = x32.bfloat16()
+    lo = (x32 - hi.float()).bfloat16()
+    return hi.to(F64), lo.to(F64)
+
+
+def x3_operands(A, W):
+    """(A3 [M, 3K], W3 [N, 3K]) with A3 . W3^T = Ahi Whi^T + Alo Whi^T + Ahi Wlo^T: what a bf16x3 kernel contracts after
+    splitting f32 operands A, W itself (the dropped lo . lo term is part of the SCHEME, not of the kernel's error)."""
+    ah, al = split_bf16(A)
+    wh, wl = split_bf16(W)
+    return torch.cat([ah, al, ah], 1), torch.cat([wh, wh, wl], 1)
+
+
+def reference_aw(A, W, op_dtype, *, bias=None, rowbias=None, rowgate=None, residual=None, residual_bcast=0, rpb=0, act=0,
+                 exact_gelu=False, plain32=True):
+    """(y, S', E_epi, y32) of the float64 operand matrices A, W (values of `op_dtype`, for the subnormal term) and the epilogue;
+    y32 = plain fp32 arithmetic on the same operands (tf32 off) for the exact-rounding-rate baseline, or None."""
+    M = A.shape[0]
+    y, s = A @ W.T, A.abs() @ W.abs().T + subnormal_term(A, W, op_dtype) / ACC      # (E_sub rides in S' through the epilogue)
+    y32 = A.float() @ W.float().T if plain32 else None
+    add32 = lambda t: None if y32 is None else y32 + t
+    b_of = torch.arange(M, device=A.device) // rpb if rpb else None
+    if bias is not None:
+        y, s, y32 = y + bias.to(F64), s + bias.to(F64).abs(), add32(bias)
+    if rowbias is not None:
+        rb = rowbias[b_of]
+        y, s, y32 = y + rb.to(F64), s + rb.to(F64).abs(), add32(rb)
+    if rowgate is not None:
+        gt = rowgate[b_of]
+        y, s, y32 = y * gt.to(F64), s * gt.to(F64).abs(), None if y32 is None else y32 * gt
+    if residual is not None:
+        r = residual[torch.arange(M, device=A.device) % rpb] if residual_bcast else residual
+        y, s, y32 = y + r.to(F64), s + r.to(F64).abs(), add32(r.float())
+    y, s, e = apply_act(y, s, act, exact_gelu=exact_gelu)
+    if act == 1 and y32 is not None:
+        y32 = F.silu(y32)
+    return y, s, e, (y32 if act in (0, 1) else None)
+
+
+def reference(a, w, *, a2=None, conv=None, **epilogue):
+    """reference_aw on the operands of a 16-bit (or bf16-triple) GEMM / conv call as the kernel is given them."""
+    A, W = operands(a, w, a2=a2, conv=conv)
+    return reference_aw(A, W, w.dtype, **epilogue)
+
+
+def run_all(fn, dt, cases):
+    """Runs every case of a table (a failure does not hide the cases after it), then reports all failures at once."""
+    errs = []
+    for name, (key, kw) in cases.items():
+        try:
+            fn(name, dt, key, **kw)
+        except AssertionError as e:
+            errs.append(str(e).split("\n")[0])
+    assert not errs, "\n".join(errs)
+
+
+# ---- the fp32-storage GEMM forms (tests/test_gpu_x3_exact.py) ----------------------------------------------------------------------
+# Accumulation constant per family, in units of S3 / S (docstring above: "fp32-storage GEMM forms").
+X3_ACC = {"x3t": ACC, "x3": ACC, "f32": ACC}
+SCHEME_REL = 3 * 2.0 ** -16       # |y3 - y| <= SCHEME_REL S: the bf16x3 scheme itself (tests/test_exact_checker.py)
+PAIR_REL = 2.0 ** -16             # |hi + lo - v| <= PAIR_REL |v|: a value carried as a bf16 hi | lo pair
+
+# The instantiations the triple-operand path (sdn_gemm_bf16 with x3_out, K' = 3K) reaches, bf16 only: the seven plain k_gemm_dma
+# tiles and the slab-ring convolution.  Not reachable with x3_out, each refused by sdn_gemm_impl: the LayerNorm-folded forms
+# (x3 && ln_c -> invalid: the precise plans normalise in f32 and write the triple), split-K (x3 && split_k > 1 -> invalid: the
+# partials would need a triple-aware reduce) and k_ffn320 (a 16-bit-only fusion with its own entry point, which takes no triples).
+# sdn_gemm_x3 / sdn_gemm_f32 (k_gemm_x3<CONV, XNJ>, k_gemm_f32 in sdn_f32.hip) keep no launch record; their tiles follow from the
+# shape by the rules restated in the case tables of tests/test_gpu_x3_exact.py.
+X3T_INSTANTIATIONS = [("dma", n, w, s, 0) for n, w, s in ((10, 4, 2), (8, 4, 2), (5, 2, 4), (5, 2, 2), (4, 2, 2), (2, 2, 2), (1, 2, 2))] \
+    + [("slab",)]
+X3_KERNELS = [("k_gemm_x3", conv, xnj) for conv in (False, True) for xnj in (5, 4)] + [("k_gemm_f32", conv) for conv in (False, True)]
+
+
+def check_split_planes(out16, f, planes):
+    """Bit equality of the bf16 planes a kernel wrote (out16 [M, planes, W]: hi | lo [| hi]) with the split of the f32 result f
+    [M, W] of the same operands: hi = RNE_bf16(f), lo = RNE_bf16(f - hi), third plane = hi.  Returns the list of what differs."""
+    hi = f.bfloat16()
+    lo = (f - hi.float()).bfloat16()
+    bits = lambda t: t.contiguous().view(torch.int16)
+    bad = []
+    if not torch.equal(bits(out16[:, 0]), bits(hi)):
+        bad.append(f"hi plane differs from bf16(f) in {int((bits(out16[:, 0]) != bits(hi)).sum())} elements")
+    if not torch.equal(bits(out16[:, 1]), bits(lo)):
+        bad.append(f"lo plane differs from bf16(f - hi) in {int((bits(out16[:, 1]) != bits(lo)).sum())} elements")
+    if planes == 3 and not torch.equal(bits(out16[:, 2]), bits(out16[:, 0])):
+        bad.append(f"third plane differs from hi in {int((bits(out16[:, 2]) != bits(out16[:, 0])).sum())} elements")
+    return bad

@@ -193,9 +193,11 @@ def expand3(w, group=None):
 
 
 def gemm_x3t(a3, w3, N, K, *, bias=None, rowbias=None, residual=None, conv=None, act=0, x3_out=1, rows_per_batch=0, out_kind=1,
-             n_valid=0):
+             n_valid=0, out=None, ldc=0):
     """sdn_gemm_bf16 over a triple A operand [M, 3K] (or an NHWC triple map for conv) and an expanded weight [N, 3K]:
-    K / Cin below are the LOGICAL sizes.  x3_out 1 -> f32 [M, N]; 2 (GEGLU) / 3 -> triple [M, 3 N'] ; 0 -> out_kind as given."""
+    K / Cin below are the LOGICAL sizes.  x3_out 1 -> f32 [M, N]; 2 (GEGLU) / 3 -> triple [M, 3 N'] ; 0 -> out_kind as given.
+    out: a caller-owned output (its first element is where the kernel starts writing) with ldc the width of one plane's row:
+    f32 rows of stride ldc, triples [hi(ldc) | lo(ldc) | hi(ldc)], pairs [hi(ldc) | lo(ldc)]; the f32 residual shares ldc."""
     d = _lib.GemmDesc()
     if conv:
         B = a3.shape[0]
@@ -211,7 +213,10 @@ def gemm_x3t(a3, w3, N, K, *, bias=None, rowbias=None, residual=None, conv=None,
     if rowbias is not None:
         d.ld_rowbias = rowbias.stride(0)
     width = N // 2 if act == 2 else N
-    if x3_out == 1:
+    d.ldc = ldc
+    if out is not None:
+        pass
+    elif x3_out == 1:
         out = torch.empty((M, width), dtype=torch.float32, device=a3.device)
     elif x3_out in (2, 3):
         out = torch.empty((M, 3 * width), dtype=BF, device=a3.device)
