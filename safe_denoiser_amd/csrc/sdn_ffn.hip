@@ -12,25 +12,41 @@
 //   X      [128 x 320]  h3 rows, 5 swizzled k-tile images (80 KB), loaded once: A operand of the projection AND of the
 //                       trailing [h3 | Wpo] k-tiles
 //   for each chunk of 64 hidden units (20 chunks; = 128 value/gate-interleaved columns of W1):
-//       acc1[128 x 128]  = X . W1_chunk^T           5 k-tiles of W1 (16 KB each) through a 2-deep LDS-DMA ring
-//       H[128 x 64]      = (LN fold) value * gelu(gate), 16 bit, written as ONE k-tile image into the ring stage just freed
-//       acc[128 x 320] += H . Wcat[:, chunk]^T      one 40 KB k-tile of the contracted output weight
+//       acc1[128 x 128]  = X . W1_chunk^T           5 k-tiles of W1 (16 KB each)
+//       H[128 x 64]      = (LN fold) value * gelu(gate), 16 bit, written as ONE k-tile image into a 16 KB buffer of its own
+//       acc[128 x 320] += H . Wcat[:, chunk]^T      the 40 KB k-tile of the contracted output weight, by column fragments
 //   acc += X . Wcat[:, 4C:]^T (5 k-tiles, double-buffered), + bias + residual x -> staged 16-bit store (+ GroupNorm column sums)
 //
 // 8 waves as 2 (M) x 4 (N): a wave owns 64 x 32 of acc1 (one value/gate fragment pair -> 16 hidden columns) and 64 x 80 of
 // acc.  Per 128 rows the L2 -> LDS traffic is 2.7 MB for 682 MFLOP (4 B/kFLOP against 15.6 for the 128 x 128 projection tile).
 //
+// All weights of the chunk loop arrive through ONE ring of four 16 KB stages, requested three slots ahead.  A chunk is 8 slots of
+// (at most) 16 MFMAs per wave, each reading one ring entry: u = 0..4 the W1 k-tiles, u = 5, 6, 7 the contraction k-tile cut by
+// output columns -- fragments {0, 1}, {2, 3}, {4} of every wave's 80 columns (16 + 16 + 8 KB; both k-steps of a fragment inside
+// its slot, so an accumulator still sees k-step 0, then 1).  Entry u lives in stage u & 3; the request for entry u + 3 is issued
+// at the top of slot u, so it has three slots (>= 1500 MFMA cycles at two waves per SIMD) to land.
+// LDS: X 80 KB | ring 4 x 16 KB | H 16 KB = 160 KB; the tail reuses ring + H as its two 40 KB weight buffers.
+//
 // Arithmetic is IDENTICAL to the two-launch path, bit for bit: same k order per output element (16x16x32 MFMA chains over
 // k-tiles 0..4 for the projection, 0..24 for the contraction, accumulators started from the bias), same LayerNorm-fold /
-// GELU / pack expressions, same residual add, same row-group order of the column sums -- tests/test_gpu_ops.py checks equality.
+// GELU / pack expressions, same residual add, same row-group order of the column sums -- tests/test_gpu_ops.py and
+// tests/test_gpu_ffn_ring.py check equality.
 //
-// LDS hazards, in program order (every wave executes the same sequence):
-//   ring stage s = g & 1 for projection k-tile g = 5 chunk + kt.  Iteration g issues k-tile g+1 into stage s^1, last read
-//   in iteration g-1 (ended by a barrier) -- or, for kt = 0, holding H of the previous chunk, whose readers (the previous
-//   contraction) are behind the barrier that ends it.  H goes into stage (5 chunk + 4) & 1, last read in iteration kt = 4.
-//   The contraction tile for a chunk arrives in 5 one-piece-per-wave slices issued AFTER each iteration's ring DMA, so the
-//   iteration's `vmcnt(1)` retires the ring k-tile (and the previous slice) while the newest slice stays in flight; the buffer
-//   was released by the barrier after the previous contraction.  `vmcnt(0)` + barrier precede every read of a buffer.
+// LDS hazards, in program order (every wave executes the same sequence; E(u) = ring entry u of the current chunk, E(8..10) =
+// E(0..2) of the next; pieces per wave: 2 per entry, 1 for E(7)):
+//   prologue   X, E(0), E(1), E(2) requested; vmcnt(0) + barrier.
+//   slot u     top: request E(u + 3) into stage (u + 3) & 3 = (u - 1) & 3, last read in slot u - 1, which ended with a barrier
+//              (slot 0: the previous chunk's slot 7).  For slot 5 the request is issued before the GEGLU arithmetic.
+//              Slot 0 first issues the 4 fold-coefficient loads of the chunk (plain loads: they count in vmcnt, between E(2), E(3)).
+//              end: E(u + 1) must have landed; E(u + 2), E(u + 3) may stay in flight:
+//                  u = 0: vmcnt(8) (E(2), the 4 coefficient loads, E(3)) | 1, 2, 3: vmcnt(4) | 4: vmcnt(3) (E(6), E(7)) |
+//                  5: vmcnt(3) (E(7), E(8)) | 6, 7: vmcnt(4).  The last chunk has no E(8..10): its slots 5..7 wait for vmcnt(0).
+//              then lgkmcnt(0) (this wave's fragment reads of stage u & 3 are done) and the barrier: every wave's pieces of
+//              E(u + 1) are visible, stage u & 3 may be refilled.
+//   H          written after slot 4's barrier, read (into registers, for all three contraction slots) in slot 5 only: its readers
+//              are behind slot 5's barrier, a whole chunk before the next write.  lgkmcnt(0) + a raw barrier publish it; neither
+//              that barrier nor the store may wait for vmcnt (the store is an asm statement for that reason, see there).
+//   tail       starts behind the last chunk's vmcnt(0) + barrier: nothing in flight, no reader left in ring or H.
 #include "sdn_gemm_common.h"
 
 namespace sdn_gemm_detail {
@@ -104,11 +120,14 @@ k_ffn320(const FfnArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int C = 320, HID = 4 * C, KT1 = C / BK, NCH = HID / 64, KT2 = NCH + KT1;      // 5 / 20 chunks / 25 contraction k-tiles
   constexpr int BM = 128, BN = C, THREADS = 512, NWAVES = 8, NREP = 5;
-  constexpr int XIMG = BM * 128;                             // one k-tile image of X or H: 16 KB
-  constexpr int W2IMG = C * 128;                             // one k-tile of the contraction weight: 40 KB
-  constexpr int OFF_W2A = KT1 * XIMG;                        // 81920
-  constexpr int OFF_RING = OFF_W2A + W2IMG;                  // 122880: ring stages 0 / 1 (16 KB each) + 8 KB = second W2 buffer (tail)
-  constexpr int LDS_BYTES = OFF_RING + W2IMG;                // 163840
+  constexpr int XIMG = BM * 128;                             // one k-tile image of X or H, one ring stage: 16 KB
+  constexpr int W2IMG = C * 128;                             // one whole k-tile of the contraction weight (tail): 40 KB
+  constexpr int NSLOT = 8, NRING = 4;                        // slots per chunk (5 W1 k-tiles + W2 slices A, B, C), ring stages
+  constexpr int OFF_RING = KT1 * XIMG;                       // 81920: ring stages 0..3 (16 KB each)
+  constexpr int OFF_H = OFF_RING + NRING * XIMG;             // 147456: H (16 KB)
+  constexpr int OFF_TA = OFF_RING, OFF_TB = OFF_RING + W2IMG;   // tail: the same 80 KB as two 40 KB weight buffers
+  constexpr int LDS_BYTES = OFF_H + XIMG;                    // 163840
+  static_assert(OFF_TB + W2IMG == LDS_BYTES && NSLOT % NRING == 0, "ring + H = the tail's two weight buffers; stage = slot & 3");
   constexpr unsigned OOB = 0x80000000u;
   __shared__ __attribute__((aligned(1024))) unsigned char smem[LDS_BYTES];
 
@@ -134,23 +153,37 @@ k_ffn320(const FfnArgs a) {
     const unsigned off = m < a.M ? (unsigned)(((long)m * C + kt * BK + lchunk * 8) * 2) : OOB;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_ptr_t)(smem + p * 1024), 16, off, 0, 0, 0);
   }
-  // projection weight k-tile g (chunk g / 5, k-tile g % 5): 16 pieces, 2 per wave
+  // Ring entry `u` of chunk jc (slot 8 jc + u) -> stage u & 3.  u = 0..4: projection weight k-tile u (16 pieces, 2 per wave);
+  // u = 5, 6: rows wn 80 + (u - 5) 32 .. + 31 of the chunk's contraction k-tile for every wn (fragments 0, 1 / 2, 3 of each wave
+  // column: 16 pieces, 2 per wave, stage row = wn 32 + local row); u = 7: rows wn 80 + 64 .. + 15 (fragment 4: 8 pieces, 1 per wave,
+  // stage row = wn 16 + local row).  u >= 8 names the next chunk's entry u - 8; past the last chunk nothing is issued.
   const unsigned w1_lane = (unsigned)(((wid * 2 * 8 + lrow) * C + lchunk * 8) * 2);
-  auto issue_w1 = [&](int g) {
-    const int jc = g / KT1, kt = g - jc * KT1;
-    unsigned char* dst = smem + OFF_RING + (g & 1) * XIMG + wid * 2048;
-    const unsigned base = w1_lane + (unsigned)((jc * 128 * C + kt * BK) * 2);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w1, (lds_ptr_t)dst, 16, base, 0, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w1, (lds_ptr_t)(dst + 1024), 16, base + (unsigned)(8 * C * 2), 0, 0, 0);
+  const unsigned w2ab_lane = (unsigned)((((wid >> 1) * 16 * NREP + (wid & 1) * 16 + lrow) * (HID + C) + lchunk * 8) * 2);
+  const unsigned w2c_lane = (unsigned)((((wid >> 1) * 16 * NREP + 64 + (wid & 1) * 8 + lrow) * (HID + C) + lchunk * 8) * 2);
+  auto issue_slot = [&](int jc, int u) {
+    if (u >= NSLOT) { u -= NSLOT; ++jc; }
+    if (jc >= NCH) return;
+    unsigned char* stage = smem + OFF_RING + (u & (NRING - 1)) * XIMG;
+    if (u < KT1) {
+      const unsigned base = w1_lane + (unsigned)((jc * 128 * C + u * BK) * 2);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w1, (lds_ptr_t)(stage + wid * 2048), 16, base, 0, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w1, (lds_ptr_t)(stage + wid * 2048 + 1024), 16, base + (unsigned)(8 * C * 2), 0, 0, 0);
+    } else if (u < NSLOT - 1) {
+      const unsigned base = w2ab_lane + (unsigned)(((u - KT1) * 32 * (HID + C) + jc * BK) * 2);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w2, (lds_ptr_t)(stage + wid * 2048), 16, base, 0, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w2, (lds_ptr_t)(stage + wid * 2048 + 1024), 16, base + (unsigned)(8 * (HID + C) * 2), 0, 0, 0);
+    } else {
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w2, (lds_ptr_t)(stage + wid * 1024), 16, w2c_lane + (unsigned)(jc * BK * 2), 0, 0, 0);
+    }
   };
-  // contraction weight k-tile t: 40 pieces, 5 per wave; slice q of a wave = piece wid * 5 + q
+  // contraction weight k-tile t as a whole (tail): 40 pieces, 5 per wave; slice q of a wave = piece wid * 5 + q
   const unsigned w2_lane = (unsigned)(((wid * 5 * 8 + lrow) * (HID + C) + lchunk * 8) * 2);
   auto issue_w2_slice = [&](int t, int q, int buf_off) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w2, (lds_ptr_t)(smem + buf_off + (wid * 5 + q) * 1024), 16,
                                              w2_lane + (unsigned)((q * 8 * (HID + C) + t * BK) * 2), 0, 0, 0);
   };
 
-  issue_w1(0);
+  issue_slot(0, 0); issue_slot(0, 1); issue_slot(0, 2);
   // accumulators of the contraction start from the bias; row statistics of this wave's rows
   f32x4 acc[4][NREP];
   {
@@ -188,19 +221,17 @@ k_ffn320(const FfnArgs a) {
   const unsigned char* sa_x = smem + (wm * 64) * 128;                       // + kt * XIMG
   SDN_FTS_MARK(0)                                                           // prologue: X + first W1 k-tile landed
   for (int jc = 0; jc < NCH; ++jc) {
+    const bool last = jc == NCH - 1;                                         // wave-uniform: entries 8..10 of the last chunk do not exist
     f32x4 acc1[4][2];
 #pragma unroll
     for (int i = 0; i < 4; ++i) { acc1[i][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc1[i][1] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-    // ---- projection: 5 k-tiles ----
+    // ---- projection: 5 k-tiles (slots u = 0..4) ----
 #pragma unroll
     for (int kt = 0; kt < KT1; ++kt) {
-      const int g = jc * KT1 + kt;
-      if (kt == 0) load_cd(jc);                                              // used after the k loop (older than the DMAs: vmcnt(1) below
-                                                                             // keeps only a slice in flight)
-      if (g + 1 < NCH * KT1) issue_w1(g + 1);
-      issue_w2_slice(jc, kt, OFF_W2A);
+      if (kt == 0) load_cd(jc);                                              // 4 loads, used after the k loop; counted in slot 0's wait
+      issue_slot(jc, kt + 3);
       const unsigned char* sa = sa_x + kt * XIMG;
-      const unsigned char* sw = smem + OFF_RING + (g & 1) * XIMG + (wn * 32) * 128;
+      const unsigned char* sw = smem + OFF_RING + (kt & (NRING - 1)) * XIMG + (wn * 32) * 128;
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         typename T::v8 fa[4], fw[2];
@@ -219,15 +250,18 @@ k_ffn320(const FfnArgs a) {
           for (int j = 0; j < 2; ++j) acc1[i][j] = T::mfma16(fw[j], fa[i], acc1[i][j]);
         __builtin_amdgcn_s_setprio(0);
       }
-      // the ring k-tile (and every older request) has landed; this iteration's W2 slice may still be in flight
       SDN_FTS_MARK(1)                                                        // projection: DMA issue + fragment reads + MFMAs issued
-      if (kt + 1 < KT1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      // entry kt + 1 has landed; entries kt + 2 and kt + 3 (2 pieces each, 1 for entry 7) stay in flight -- and in slot 0 the
+      // 4 fold-coefficient loads, which sit between them in issue order
+      if (kt == 0) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      else if (kt < KT1 - 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                     // fragment reads done before the stage is refilled
       SDN_FTS_MARK(2)                                                        // ... wait for the next k-tile
       __builtin_amdgcn_s_barrier();
       SDN_FTS_MARK(3)                                                        // ... barrier
     }
+    issue_slot(jc, KT1 + 3);                                                 // slot 5's request, ahead of the GEGLU arithmetic
     if (own_stats && jc == 0) {                                  // as k_gemm_dma (LNF = 1): the other three lane groups hold the rest of a row
       const float invk = 1.0f / (float)C;
 #pragma unroll
@@ -240,8 +274,9 @@ k_ffn320(const FfnArgs a) {
         ln_mu[i] = mu; ln_rs[i] = __builtin_amdgcn_rsqf(var + 1e-5f);
       }
     }
-    // ---- GEGLU: LayerNorm fold, value * gelu(gate), 16 bit -> H (a k-tile image in the stage read last) ----
-    unsigned char* sh = smem + OFF_RING + ((jc * KT1 + KT1 - 1) & 1) * XIMG;
+    // ---- GEGLU: LayerNorm fold, value * gelu(gate), 16 bit -> H (a k-tile image of its own) ----
+    unsigned char* sh = smem + OFF_H;
+    unsigned h_addr = 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int row = wm * 64 + i * 16 + fr;
@@ -250,20 +285,54 @@ k_ffn320(const FfnArgs a) {
       uint2 pk;
       pk.x = T::pack2(hv[0] * gelu_erf(gv[0]), hv[1] * gelu_erf(gv[1]));
       pk.y = T::pack2(hv[2] * gelu_erf(gv[2]), hv[3] * gelu_erf(gv[3]));
-      *reinterpret_cast<uint2*>(sh + lds_off(row, wn * 2 + (fq >> 1)) + (fq & 1) * 8) = pk;
+      if (i == 0) h_addr = (unsigned)(unsigned long)(lds_ptr_t)(sh + lds_off(row, wn * 2 + (fq >> 1)) + (fq & 1) * 8);
+      // stored from an asm statement: before a ds_write of its own the compiler waits for vmcnt(0) (LDS-DMA may alias it), which
+      // would drain the ring here once per chunk.  Rows i 16 + .. share the swizzle of row 0 + ..: 2 KiB apart
+      asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(h_addr), "v"((unsigned long long)pk.y << 32 | pk.x), "i"(i * 16 * 128) : "memory");
     }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                       // the H stores above are not counted by the compiler
     SDN_FTS_MARK(4)                                                          // GEGLU epilogue (waits for the MFMAs)
-    __syncthreads();                                                         // H visible (no DMA outstanding: vmcnt(0) above)
+    __builtin_amdgcn_s_barrier();                                            // H visible (raw: __syncthreads would drain the ring)
+    asm volatile("" ::: "memory");
     SDN_FTS_MARK(5)                                                          // barrier
-    // ---- contraction with this chunk's k-tile ----
+    // ---- contraction with this chunk's k-tile, by column fragments: slots 5, 6, 7 = fragments {0, 1}, {2, 3}, {4} of each wave,
+    //      both k-steps of a fragment inside its slot (per accumulator: k-step 0, then 1, as in the whole-tile form) ----
     {
-      const unsigned char* sa = sh + (wm * 64) * 128;
-      const unsigned char* sw = smem + OFF_W2A + (wn * 16 * NREP) * 128;
-      SDN_FFN_CONTRACT(sa, sw)
+      typename T::v8 fa[2][4];
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          fa[ks][i] = *reinterpret_cast<const typename T::v8*>(sh + (wm * 64) * 128 + lds_off(i * 16 + fr, ks * 4 + fq));
+#pragma unroll
+      for (int v = 0; v < 3; ++v) {
+        const int u = KT1 + v, nj = v == 2 ? 1 : 2;
+        if (v > 0) issue_slot(jc, u + 3);
+        const unsigned char* sw = smem + OFF_RING + (u & (NRING - 1)) * XIMG + (wn * 16 * nj) * 128;
+        typename T::v8 fw[2][2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+          for (int j = 0; j < nj; ++j) fw[ks][j] = *reinterpret_cast<const typename T::v8*>(sw + lds_off(j * 16 + fr, ks * 4 + fq));
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < nj; ++j) acc[i][2 * v + j] = T::mfma16(fw[ks][j], fa[ks][i], acc[i][2 * v + j]);
+        __builtin_amdgcn_s_setprio(0);
+        SDN_FTS_MARK(6)                                                      // contraction: request + fragment reads + MFMAs issued
+        // the next entry has landed; the two after it stay in flight (slot 5: entries 7 (1 piece), 8; slots 6, 7: 2 + 2 pieces).
+        // The last chunk has no entries 8..10: it drains what is left
+        if (last) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else if (v == 0) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                                        // the stage (after slot 5: H too) is free again
+        SDN_FTS_MARK(5)
+      }
     }
-    SDN_FTS_MARK(6)                                                          // contraction: fragment reads + MFMAs issued
-    __syncthreads();                                                         // H's stage and the W2 buffer are free again
-    SDN_FTS_MARK(5)
   }
 
   // ---- trailing k-tiles [h3 | Wpo]: A = X, weights double-buffered between the two 40 KB buffers.  The residual tile (80 KB of
@@ -282,12 +351,12 @@ k_ffn320(const FfnArgs a) {
     }
   };
 #pragma unroll
-  for (int q = 0; q < 5; ++q) issue_w2_slice(NCH, q, OFF_W2A);
+  for (int q = 0; q < 5; ++q) issue_w2_slice(NCH, q, OFF_TA);
 #pragma unroll
-  for (int q = 0; q < 5; ++q) issue_w2_slice(NCH + 1, q, OFF_RING);
+  for (int q = 0; q < 5; ++q) issue_w2_slice(NCH + 1, q, OFF_TB);
 #pragma unroll
   for (int kt = 0; kt < KT1; ++kt) {
-    const int boff = (kt & 1) ? OFF_RING : OFF_W2A;
+    const int boff = (kt & 1) ? OFF_TB : OFF_TA;
     // this k-tile's weights have landed; what was issued after them may stay in flight (in issue order: kt = 0: W2[1] |
     // 1: W2[2], res0 | 2: res0?, W2[3], res1 | 3: res1, W2[4], res2 | 4: res2, res3)
     if (kt == 0) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");

@@ -34,7 +34,7 @@ lib.sdn_debug_set_ffn_stamps(None)
 s = st.cpu().reshape(-1, 8).double()
 s = s[s.sum(1) > 0]
 names = ["prologue (X + first W1 k-tile)", "projection: issue, reads, MFMAs", "projection: wait for next k-tile", "projection: barrier",
-         "GEGLU epilogue", "barriers around the contraction", "contraction: reads, MFMAs", "trailing k-tiles + final epilogue"]
+         "GEGLU epilogue", "contraction: waits + barriers", "contraction: issue, reads, MFMAs", "trailing k-tiles + final epilogue"]
 tot = s.sum(1).median()
 print(f"{len(s)} waves; {tot:9.0f} ticks per wave = one 128-row block (20 chunks)")
 for i, n in enumerate(names):
