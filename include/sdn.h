@@ -745,6 +745,23 @@ int sdn_image_resize_u8(const uint8_t* in, int32_t batch, int32_t in_size, int32
                         const int32_t* bounds, int32_t ksize, uint8_t* tmp, uint8_t* out, void* stream);
 int sdn_clip_normalize_u8(const uint8_t* in, int32_t batch, int32_t size, float mean_r, float mean_g, float mean_b, float std_r,
                           float std_g, float std_b, float* out, void* stream);
+/* ---- image metrics: the scoring head of the CLIP score and of the aesthetic score ------------------------------------------------
+ * Replaces the per-sample arithmetic of torchmetrics' CLIPScore.update (third party; driven by evaluations/base_image.py:145-157:
+ * `img / img.norm(p=2, dim=-1, keepdim=True)`, the same for the text features, `100 * (img * txt).sum(axis=-1)`) and of AE.forward
+ * (evaluations/utils/aes.py:23-35: `emb / torch.norm(emb, dim=-1, keepdim=True)` through AE_MLP, five Linears with no activation
+ * between them = one affine map, composed by the caller).
+ *   out[i] = scale * < x_i / |x_i| , y'_j > + bias      j = i (y_rows == rows) or j = 0 (y_rows == 1)
+ *   y' = y_j / |y_j| when normalize_y, else y_j.  f32 accumulation, out f32 [rows], dense.
+ *   x: [rows, dim] of dtype_x (0 bf16, 1 fp16, 2 f32), row stride ldx ELEMENTS; y likewise (dtype_y, ldy).
+ * Paired rows with normalize_y = 1, scale = 100, bias = 0 is the CLIP score of each pair; y_rows = 1, normalize_y = 0, scale = 1,
+ * bias = b is the aesthetic head w . x^ + b.  One pass over each row (sum x y, sum x^2, and sum y^2 when asked), one wave per row.
+ * Any dim >= 1; nothing at or past column dim of a row is read.  A zero-norm row yields NaN, as the torch expression does.
+ * No allocation, no synchronisation; rows == 0 launches nothing.  SDN_E_INVALID: a null pointer with rows > 0, dim < 1, y_rows not
+ * in {1, rows}, ld < dim, a dtype code outside 0..2, x or y not 16-byte aligned, out not 4-byte aligned.  A row pitch that is a
+ * multiple of 16 bytes selects the vector loads; any other pitch >= dim (a dense [rows, 7] matrix) is read element by element. */
+int sdn_embed_row_scores(const void* x, int32_t dtype_x, int64_t ldx, const void* y, int32_t dtype_y, int64_t ldy,
+                         int32_t y_rows, int32_t rows, int32_t dim, int32_t normalize_y, float scale, float bias,
+                         float* out, void* stream);
 /* The transform of the negative reference images (data/dataloader.py:46-78: `transforms.Resize((512, 512))` on a PIL image =
  * `Image.resize((512, 512), BILINEAR)`, then ToTensor and Normalize(.5, .5)), for a batch of equally sized RGB images of ANY
  * aspect ratio.

@@ -404,7 +404,7 @@ class _QueuedLogger:
 
 def run_job(args, pipe, repellency_processor=None, task_config: Optional[Mapping[str, Any]] = None, eval_func: Optional[Callable] = None,
             prompts_per_batch: int = 64, rank: int = 0, world: int = 1, device="cuda", overlap_io: Optional[bool] = None,
-            max_overfill: float = 0.25, timings: Optional[dict] = None) -> RunArtifacts:
+            max_overfill: float = 0.25, timings: Optional[dict] = None, metrics: Optional[Mapping[str, Any]] = None) -> RunArtifacts:
     """The body of the reference's main() after model loading (run_nudity.py:341-529) on the batched engine: read the prompt
     table (`args.data`, `--valid_case_numbers`), shard it over the ranks, and for every batch of prompts (each with its own
     guidance scale and seed) call `pipe(prompt, ..., negative_prompt, negative_prompt_space, generator, repellency_processor, safree_dict,
@@ -414,7 +414,12 @@ def run_job(args, pipe, repellency_processor=None, task_config: Optional[Mapping
     host memory asynchronously and written / classified / logged by a worker thread while the GPU runs batch k + 1 (the reference
     is serial: per image two or three PNG encodes + the classifier sit between two pipeline calls, :462-504); the output files
     are identical to the serial ones.  `max_overfill`: cases.batches' tail policy (0 = never exceed `prompts_per_batch`).
-    `timings`: a dict that receives {batches: [{prompts, gpu_s}], host_io_s, total_s} (bench.py's job leg)."""
+    `timings`: a dict that receives {batches: [{prompts, gpu_s}], host_io_s, total_s} (bench.py's job leg).
+    `metrics`: name -> scorer (safe_denoiser_amd.metrics.CLIPScore / AestheticScore, or anything with `update(images, prompts)`,
+    `compute()` and `state()`).  Every scorer sees each batch straight after the pipeline call -- in the overlapped path the uint8
+    DEVICE tensor, before its copy to the host and on the same stream (no extra synchronisation); in the serial path the PIL
+    images -- and `{save_dir}/metrics.yaml` (the rank's own directory when world > 1) = {name: {value, sum, n}} is written after
+    the tree is finished.  Ranks are not merged.  With None nothing changes."""
     import time
 
     from . import cases as _cases
@@ -479,6 +484,8 @@ def run_job(args, pipe, repellency_processor=None, task_config: Optional[Mapping
                 t0 = time.time()
                 imgs = call(batch, "pil", log)
                 dt = time.time() - t0
+                for scorer in (metrics or {}).values():
+                    scorer.update(imgs, [c["prompt"] for c in batch])
                 t1 = time.perf_counter()
                 write_batch(batch, imgs, dt)
                 stats["host_io_s"] += time.perf_counter() - t1
@@ -491,6 +498,8 @@ def run_job(args, pipe, repellency_processor=None, task_config: Optional[Mapping
             writer.acquire_slot()                                   # at most `depth` batches of images in flight
             t0 = time.time()
             u8 = call(batch, "uint8", qlog)                         # [P, H, W, 3] uint8 on the device: what numpy_to_pil would build
+            for scorer in (metrics or {}).values():                 # stream-ordered device work on the decoded batch, no sync
+                scorer.update(u8, [c["prompt"] for c in batch])
             if u8.is_cuda:
                 host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
                 host.copy_(u8, non_blocking=True)
@@ -516,6 +525,14 @@ def run_job(args, pipe, repellency_processor=None, task_config: Optional[Mapping
             if pool is not None:
                 pool.shutdown(wait=True)
     art.finish(dataset_size=len(table))
+    if metrics is not None:
+        import yaml
+        report = {}
+        for name, scorer in metrics.items():
+            total, n = scorer.state()
+            report[name] = {"value": float(scorer.compute()) if n else None, "sum": float(total), "n": int(n)}
+        with open(os.path.join(art.save_dir, "metrics.yaml"), "w") as f:
+            yaml.dump(report, f)
     stats["total_s"] = time.perf_counter() - t_job
     if timings is not None:
         timings.update(stats)
