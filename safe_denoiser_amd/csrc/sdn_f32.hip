@@ -1168,6 +1168,7 @@ static int groupnorm_f32_impl(int triple, const void* x, const void* x2, int32_t
     int rpc = 16;                                                            // rows per chunk: >= 16, at most 64 chunks per sample
     while ((hw + rpc - 1) / rpc > 64) rpc *= 2;
     const int nchunk = (hw + rpc - 1) / rpc;
+    record_norm_launch({6, 2, 0, 0, 0, 0, 0, 0, rpc, nchunk, 0, triple});
     hipLaunchKernelGGL(k_gn_rows_stats, dim3((unsigned)(batch * nchunk)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
                        (const float*)x2, hw, c1, c2, groups, rpc, (double*)stats_ws);
     hipLaunchKernelGGL(k_gn_rows_apply, dim3((unsigned)(batch * nchunk)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
@@ -1176,6 +1177,7 @@ static int groupnorm_f32_impl(int triple, const void* x, const void* x2, int32_t
   }
   const bool pairs = (cpg & 1) == 0 && (c1 & 1) == 0 && cpg <= 512 && (reinterpret_cast<uintptr_t>(x) & 7) == 0 &&
                      (reinterpret_cast<uintptr_t>(out) & 7) == 0 && (!x2 || (reinterpret_cast<uintptr_t>(x2) & 7) == 0);
+  record_norm_launch({pairs ? 7 : 8, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, triple});
   if (pairs)
     hipLaunchKernelGGL(k_groupnorm_f32, dim3((unsigned)(batch * groups)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
                        (const float*)x2, hw, c1, c2, groups, eps, silu, gamma, beta, (float*)out, triple);
@@ -1245,7 +1247,9 @@ static int layernorm_f32_impl(int triple, const void* x, int64_t rows, int32_t c
                               void* out, void* stream) {
   if (!x || !gamma || !beta || !out || rows < 0 || c <= 0 || (triple && (reinterpret_cast<uintptr_t>(out) & 3))) return SDN_E_INVALID;
   if (rows == 0) return SDN_OK;
-  if ((c & 3) == 0 && c <= 64 * 4 * LN_MAXV && al16(x) && al16(gamma) && al16(beta) && (reinterpret_cast<uintptr_t>(out) & (triple ? 7 : 15)) == 0)
+  const bool regs = (c & 3) == 0 && c <= 64 * 4 * LN_MAXV && al16(x) && al16(gamma) && al16(beta) && (reinterpret_cast<uintptr_t>(out) & (triple ? 7 : 15)) == 0;
+  record_norm_launch({regs ? 9 : 10, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, triple});
+  if (regs)
     hipLaunchKernelGGL(k_layernorm_f32_regs, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
                        (long)rows, c, eps, gamma, beta, (float*)out, triple);
   else
@@ -1417,8 +1421,9 @@ extern "C" int sdn_layernorm_mod_f32(const void* x, int64_t rows, int32_t c, flo
   const long blocks = (rows + 3) / 4;
   if (blocks > 0x7fffffffL) return SDN_E_INVALID;
 #define SDN_LNM_F32(NV)                                                                                                         \
-  hipLaunchKernelGGL((k_layernorm_mod_f32<NV>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)x, (long)rows, \
-                     c, eps, scale, shift, ld_mod, rows_per_batch, (float*)out)
+  do { hipLaunchKernelGGL((k_layernorm_mod_f32<NV>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)x, (long)rows, \
+                     c, eps, scale, shift, ld_mod, rows_per_batch, (float*)out);                                                \
+  record_norm_launch({11, 2, NV, 0, 0, 0, 0, 0, 0, 0, 0, 0}); } while (0)
   if (c <= 512) SDN_LNM_F32(2);
   else if (c <= 1024) SDN_LNM_F32(4);
   else SDN_LNM_F32(8);

@@ -420,10 +420,12 @@ int groupnorm_impl(const void* x, const void* x2, int32_t batch, int32_t hw, int
   if (lds > 64 * 1024) return SDN_E_INVALID;
   if (cols1) {                                // statistics from the producers' column partials: no pass over x
     if ((hw & 127) || (c2 > 0 && !cols2)) return SDN_E_INVALID;
+    record_norm_launch({2, T::kDtype, 0, 0, 0, 0, 0, 0, 0, 0, 1, 0});
     hipLaunchKernelGGL(k_gn_finalize_cols, dim3(batch, groups), dim3(256), 0, st, cols1, cols2, hw / 128, c1, c2, groups,
                        (float)hw * (float)(C / groups), eps, stats_ws);
   } else {
     float* partials = stats_ws + (size_t)batch * groups * 2;          // [B][ntiles][G][2] after the final stats
+    record_norm_launch({1, T::kDtype, 0, 0, nch, ct, ntiles, rows_per_tile, 0, 0, 0, 0});
     hipLaunchKernelGGL((k_gn_stats<T>), dim3(batch, ntiles), dim3(THREADS), lds, st, (const unsigned short*)x,
                        (const unsigned short*)x2, hw, c1, c2, groups, rows_per_tile, ct, nch, partials);
     hipLaunchKernelGGL(k_gn_finalize, dim3(batch), dim3(512), 0, st, partials, ntiles, groups,
@@ -446,9 +448,10 @@ int layernorm_impl(const void* x, int64_t rows, int32_t c, float eps, const floa
   if (mod && (rows_per_batch <= 0 || ld_mod < c || (ld_mod & 3))) return SDN_E_INVALID;
   if (rows == 0) return SDN_OK;
 #define SDN_LN_LAUNCH(NQ, R)                                                                                          \
-  hipLaunchKernelGGL((k_layernorm<T, NQ, R>), dim3((unsigned)((rows + 4 * (R) - 1) / (4 * (R)))), dim3(THREADS), 0,      \
+  do { hipLaunchKernelGGL((k_layernorm<T, NQ, R>), dim3((unsigned)((rows + 4 * (R) - 1) / (4 * (R)))), dim3(THREADS), 0,      \
                      (hipStream_t)stream, (const unsigned short*)x, (long)rows, c, eps, gamma, beta, (unsigned short*)out, \
-                     mod, rows_per_batch, ld_mod)
+                     mod, rows_per_batch, ld_mod);                                                                     \
+  record_norm_launch({mod ? 4 : 3, T::kDtype, NQ, R, 0, 0, 0, 0, 0, 0, 0, 0}); } while (0)
   if (c <= 512) SDN_LN_LAUNCH(1, 4);
   else if (c <= 1024) SDN_LN_LAUNCH(2, 2);
   else SDN_LN_LAUNCH(4, 1);
@@ -537,8 +540,9 @@ int row_stats_impl(const void* x, int64_t rows, int32_t c, float eps, float* out
   if (!x || !out || rows < 0 || c <= 0 || (c & 7) || c > 2048 || !al16(x) || (reinterpret_cast<uintptr_t>(out) & 7)) return SDN_E_INVALID;
   if (rows == 0) return SDN_OK;
 #define SDN_RS_LAUNCH(NQ, R)                                                                                          \
-  hipLaunchKernelGGL((k_row_stats<T, NQ, R>), dim3((unsigned)((rows + 4 * (R) - 1) / (4 * (R)))), dim3(THREADS), 0,      \
-                     (hipStream_t)stream, (const unsigned short*)x, (long)rows, c, eps, out)
+  do { hipLaunchKernelGGL((k_row_stats<T, NQ, R>), dim3((unsigned)((rows + 4 * (R) - 1) / (4 * (R)))), dim3(THREADS), 0,      \
+                     (hipStream_t)stream, (const unsigned short*)x, (long)rows, c, eps, out);                            \
+  record_norm_launch({5, T::kDtype, NQ, R, 0, 0, 0, 0, 0, 0, 0, 0}); } while (0)
   if (c <= 512) SDN_RS_LAUNCH(1, 4);
   else if (c <= 1024) SDN_RS_LAUNCH(2, 2);
   else SDN_RS_LAUNCH(4, 1);
@@ -561,6 +565,17 @@ int sdn_set_scalar(float* dst, float v, void* stream) {
   return sdn_launch_status();
 }
 using namespace sdn_norm_detail;
+
+// diagnostics (tests): what the last launch of the normalisation family ran (sdn_ops.h: sdn_norm_launch), so that a test written
+// for one kernel form notices when the dispatch moves its shape to another
+static int g_last_norm_launch[SDN_NL_COUNT] = {0};
+void record_norm_launch(const sdn_norm_launch& l) {
+  const int v[SDN_NL_COUNT] = {l.kernel, l.dtype, l.nq, l.r, l.nch, l.ct, l.ntiles, l.rows_per_tile, l.rpc, l.nchunk, l.stats_src, l.triple};
+  for (int i = 0; i < SDN_NL_COUNT; ++i) g_last_norm_launch[i] = v[i];
+}
+extern "C" void sdn_debug_norm_last_launch(int* out, int n) {
+  for (int i = 0; out && i < n; ++i) out[i] = i < SDN_NL_COUNT ? g_last_norm_launch[i] : 0;
+}
 
 #define SDN_NORM_ENTRY(SUF, T)                                                                                          \
   extern "C" int sdn_groupnorm_##SUF(const void* x, const void* x2, int32_t batch, int32_t hw, int32_t c1, int32_t c2, \

@@ -27,3 +27,13 @@ int sdn_linear_pair_fold(int dtype, const void* wa, const void* wb, const float*
 // 3x3 convolutions the slab-ring kernel (sdn_conv.hip) takes over from the implicit-GEMM tile: shape part of the test
 // (square side x side map, M = batch * side^2 output rows, N padded output channels).
 int sdn_conv_slab_shape_ok(int M, int N, int Cin, int side, int stride, int upsample, int asym_pad, int out_kind, int n_valid);
+
+// Launch record of the normalisation family (host side, diagnostics only: sdn_debug_norm_last_launch), set by the launchers of
+// sdn_norm.hip and sdn_f32.hip where the kernel is chosen.  kernel: 1 k_gn_stats + k_gn_finalize + k_gn_apply, 2 k_gn_finalize_cols
+// + k_gn_apply, 3 k_layernorm, 4 k_layernorm (adaLN), 5 k_row_stats, 6 k_gn_rows_stats + k_gn_rows_apply, 7 k_groupnorm_f32,
+// 8 k_groupnorm_f32_any, 9 k_layernorm_f32_regs, 10 k_layernorm_f32, 11 k_layernorm_mod_f32.  dtype: 0 bf16, 1 f16, 2 f32.
+// Fields a kernel does not have are 0.
+enum { SDN_NL_KERNEL, SDN_NL_DTYPE, SDN_NL_NQ, SDN_NL_R, SDN_NL_NCH, SDN_NL_CT, SDN_NL_NTILES, SDN_NL_ROWS_PER_TILE, SDN_NL_RPC,
+       SDN_NL_NCHUNK, SDN_NL_STATS_SRC, SDN_NL_TRIPLE, SDN_NL_COUNT };
+struct sdn_norm_launch { int kernel, dtype, nq, r, nch, ct, ntiles, rows_per_tile, rpc, nchunk, stats_src, triple; };
+void record_norm_launch(const sdn_norm_launch& l);

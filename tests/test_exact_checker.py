@@ -258,3 +258,198 @@ def test_split_planes_check_and_plane_guards():
 def test_x3t_instantiation_list_is_the_plain_part_of_the_16_bit_one():
     """The triple-operand path reaches the plain k_gemm_dma tiles and the slab ring, nothing else (exact.py says why)."""
     assert set(X.X3T_INSTANTIATIONS) == {k for k in X.INSTANTIATIONS if k[0] == "dma" and k[4] == 0} | {("slab",)}
+
+
+# ---- the normalisation kernels: the dispatch lists, the constants' hard bounds, emulations and planted faults --------------------
+from tests_support import norm_cases as NC  # noqa: E402
+
+
+def _src(name):
+    return open(os.path.join(ROOT, "safe_denoiser_amd", "csrc", name)).read()
+
+
+def _body(src, head):
+    """The function whose definition starts with `head`, up to the first line that is a lone closing brace."""
+    i = src.index(head)
+    return src[i:src.index("\n}\n", i)]
+
+
+def test_norm_dispatch_matches_the_instantiation_list():
+    """Parses the launchers of sdn_norm.hip and sdn_f32.hip: the template instantiations and kernel forms they can launch are the
+    NORM_INSTANTIATIONS the GPU matrix covers, every launch site leaves a record, and no normalisation kernel exists outside them."""
+    norm, f32 = _src("sdn_norm.hip"), _src("sdn_f32.hip")
+    pairs = lambda body, macro: {(int(a), int(b)) for a, b in re.findall(macro + r"\((\d+),\s*(\d+)\);", body)}
+    launched = lambda body: set(re.findall(r"hipLaunchKernelGGL\(\(?(k_\w+)", body))
+    found = set()
+    ln = _body(norm, "int layernorm_impl(")
+    assert "record_norm_launch({mod ? 4 : 3, T::kDtype, NQ, R," in ln and launched(ln) == {"k_layernorm"}
+    found |= {(k, nq, r) for k in ("layernorm", "layernorm_mod") for nq, r in pairs(ln, "SDN_LN_LAUNCH")}
+    assert "layernorm_impl<T>(x, rows, c, eps, scale, shift, out, stream, 1, rows_per_batch, ld_mod)" in norm      # adaLN = mod 1
+    rs = _body(norm, "int row_stats_impl(")
+    assert "record_norm_launch({5, T::kDtype, NQ, R," in rs and launched(rs) == {"k_row_stats"}
+    found |= {("row_stats", nq, r) for nq, r in pairs(rs, "SDN_RS_LAUNCH")}
+    gn = _body(norm, "int groupnorm_impl(")
+    assert launched(gn) == {"k_gn_finalize_cols", "k_gn_stats", "k_gn_finalize", "k_gn_apply"}
+    assert "record_norm_launch({2, T::kDtype," in gn and "record_norm_launch({1, T::kDtype, 0, 0, nch, ct, ntiles, rows_per_tile," in gn
+    found |= {("gn_stats", 0, 0), ("gn_cols", 0, 0)}
+    gf = _body(f32, "static int groupnorm_f32_impl(")
+    assert launched(gf) == {"k_gn_rows_stats", "k_gn_rows_apply", "k_groupnorm_f32", "k_groupnorm_f32_any"}
+    assert "record_norm_launch({6, 2, 0, 0, 0, 0, 0, 0, rpc, nchunk, 0, triple})" in gf and "record_norm_launch({pairs ? 7 : 8, 2," in gf
+    found |= {("gn_f32_rows", 0, 0), ("gn_f32_pairs", 0, 0), ("gn_f32_any", 0, 0)}
+    lf = _body(f32, "static int layernorm_f32_impl(")
+    assert launched(lf) == {"k_layernorm_f32_regs", "k_layernorm_f32"} and "record_norm_launch({regs ? 9 : 10, 2," in lf
+    found |= {("ln_f32_regs", 0, 0), ("ln_f32", 0, 0)}
+    lm = _body(f32, 'extern "C" int sdn_layernorm_mod_f32(')
+    assert launched(lm) == {"k_layernorm_mod_f32<NV>"} or launched(lm) == {"k_layernorm_mod_f32"}
+    assert "record_norm_launch({11, 2, NV," in lm
+    found |= {("ln_mod_f32", int(nv), 0) for nv in re.findall(r"SDN_LNM_F32\((\d+)\);", lm)}
+    assert found == set(X.NORM_INSTANTIATIONS), dict(missing_from_matrix=sorted(found - set(X.NORM_INSTANTIATIONS)),
+                                                     not_in_dispatch=sorted(set(X.NORM_INSTANTIATIONS) - found))
+    # the widths at which the GPU cases switch instantiation are the launchers' thresholds
+    assert "if (c <= 512) SDN_LN_LAUNCH(1, 4);" in ln and "else if (c <= 1024) SDN_LN_LAUNCH(2, 2);" in ln
+    assert [NC.ln16_nq_r(c) for c in (512, 520, 1024, 1032)] == [(1, 4), (2, 2), (2, 2), (4, 1)]
+    # every normalisation kernel of the two files is launched by one of the launchers above
+    kernels = {k for src in (norm, f32) for k in re.findall(r"\n(k_\w+)\(", src) if re.search(r"norm|k_gn_|row_stats", k)}
+    assert kernels == {"k_gn_stats", "k_gn_finalize", "k_gn_finalize_cols", "k_gn_apply", "k_layernorm", "k_row_stats", "k_groupnorm_f32",
+                       "k_groupnorm_f32_any", "k_gn_rows_stats", "k_gn_rows_apply", "k_layernorm_f32", "k_layernorm_f32_regs",
+                       "k_layernorm_mod_f32"}, kernels
+    assert sorted(X.NORM_KERNEL) == list(range(1, 12)) and X.norm_coverage_wanted() and len(X.NL_FIELDS) == 12
+    assert "enum { SDN_NL_KERNEL, SDN_NL_DTYPE, SDN_NL_NQ, SDN_NL_R, SDN_NL_NCH, SDN_NL_CT, SDN_NL_NTILES, SDN_NL_ROWS_PER_TILE, SDN_NL_RPC," in _src("sdn_ops.h")
+    assert "sdn_debug_norm_last_launch" not in open(os.path.join(ROOT, "include", "sdn.h")).read()
+
+
+def test_norm_launch_plans_restate_the_launcher():
+    """norm_cases.gn16_plan against the arithmetic of groupnorm_impl as written, and the shapes the issue names."""
+    gn = _body(_src("sdn_norm.hip"), "int groupnorm_impl(")
+    for line in ("int nch = (cch + THREADS - 1) / THREADS;", "while (cch % nch != 0) ++nch;", "if (ct > THREADS) return SDN_E_INVALID;",
+                 "int ntiles = (hw + 31) / 32;", "if (ntiles > GN_MAX_TILES) ntiles = GN_MAX_TILES;",
+                 "const int rows_per_tile = (hw + ntiles - 1) / ntiles;", "if (lds > 64 * 1024) return SDN_E_INVALID;"):
+        assert line in gn, line
+    for c in NC.GN16_CASES.values():
+        p = NC.gn16_plan(c["hw"], c["C"])
+        assert all(p[k] == v for k, v in c["plan"].items()), (c, p)
+    assert NC.gn16_plan(33, 2056) is None and NC.gn16_plan(33, 320)["rt"] == 6 and NC.gn16_plan(33, 4096)["rt"] == 1
+    assert NC.gnf32_rpc(1025) == (32, 33) and NC.gnf32_rpc(2049) == (64, 33) and NC.gnf32_rpc(17) == (16, 2)
+
+
+def test_norm_constants_stay_below_their_hard_bounds():
+    """ARITH <= 8 roundings; every family's STAT below (longest serial fp32 chain of its statistics) x 2^-24, and not below the
+    2^-24 of a single rounding."""
+    assert all(v <= 8 * 2.0 ** -24 for v in X.NORM_ARITH.values())
+    chains = NC.stat_chains()
+    assert set(chains) == set(X.NORM_STAT)
+    for fam, stat in X.NORM_STAT.items():
+        assert 2.0 ** -24 <= stat < chains[fam] * 2.0 ** -24, (fam, stat, chains[fam])
+
+
+def _gn_ref(x, G, gamma, beta, eps, silu, family="gn16"):
+    B, hw, Cc = x.shape
+    return X.norm_reference(x.double().view(B, hw, G, Cc // G), gamma.double().view(1, 1, G, -1), beta.double().view(1, 1, G, -1), (1, 3), eps,
+                            e2=True, family=family, act=silu)
+
+
+def _norm_verdict(out, ref, dt, *, mean=None, rstd=None, family=None, ref32=None):
+    st = X.analyse(out.reshape(ref["y"].shape), ref["y"], ref["s"], ref["e"], dtype=dt)
+    f = X.failures(st, exact_fn=ref32 is not None, ref_rate=None if ref32 is None else X.ref_rate(ref32.reshape(ref["y"].shape), ref["y"], dt))
+    if mean is not None:
+        f += X.stat_failures(X.stat_errors(mean.reshape(ref["mu"].shape), rstd.reshape(ref["mu"].shape), ref), X.NORM_STAT[family])
+    return f
+
+
+GN_EMU_CASES = ["ragged tile: hw 33, C 320, cpg 10, rt 6", "tile cap: hw 4097 -> 33 rows per tile", "uneven tiles: hw 100, G 1",
+                "two sources 320 + 640, seam inside group 10", "prime chunk count: C 1928 (241 chunks), G 8"]
+
+
+@pytest.fixture(scope="module")
+def gn_emulation_inputs():
+    """The GPU tests' own inputs and float64 references of the emulated GroupNorm cases, per (case, dtype); never modified."""
+    made = {}
+    for name in GN_EMU_CASES:
+        c = NC.GN16_CASES[name]
+        for dt in DTYPES:
+            x = NC.gn_input(2, c["hw"], c["C"], dt, seed=len(name))
+            gamma, beta = NC.affine(c["C"], beta0=c.get("beta0", 0.0))
+            fam = c.get("family", "gn16")
+            made[name, dt] = dict(x=x, gamma=gamma, beta=beta, G=c["G"], family=fam,
+                                  ref={s: _gn_ref(x, c["G"], gamma, beta, 1e-5, s, family=fam) for s in (0, 1)})
+    return made
+
+
+@pytest.mark.parametrize("dt", DTYPES, ids=["bf16", "f16"])
+@pytest.mark.parametrize("name", GN_EMU_CASES)
+def test_groupnorm_emulation_passes_the_criterion(gn_emulation_inputs, name, dt):
+    """fp32 arithmetic with the kernel's summation structure (per-tile partials, serial group reduction, 8-share finalize,
+    E[x^2] - mean^2, x * ca + cb) on the GPU cases' inputs: inside the bound, statistics inside theirs, clean share >= 98 %."""
+    em = gn_emulation_inputs[name, dt]
+    for silu in (0, 1):
+        out, mean, rstd = NC.emulate_gn16(em["x"], em["G"], 1e-5, em["gamma"], em["beta"], silu, dt)
+        assert _norm_verdict(out, em["ref"][silu], dt, mean=mean, rstd=rstd, family=em["family"]) == [], (name, silu)
+        assert X.clean_share(em["ref"][silu], dt) >= X.CLEAN_SHARE_MIN
+
+
+@pytest.mark.parametrize("dt", DTYPES, ids=["bf16", "f16"])
+@pytest.mark.parametrize("fault", ["drop_row", "next_group_chunk", "n_minus_1", "eps_outside", "affine_shift", "rtz"])
+def test_groupnorm_planted_fault_is_found(gn_emulation_inputs, fault, dt):
+    """Each fault the relative-L2 tests cannot see must be rejected, at the ragged-tile shape and at the hw = 4097 one."""
+    for name in GN_EMU_CASES[:2]:
+        em = gn_emulation_inputs[name, dt]
+        out, mean, rstd = NC.emulate_gn16(em["x"], em["G"], 1e-5, em["gamma"], em["beta"], 0, dt, fault=fault)
+        f = _norm_verdict(out, em["ref"][0], dt, mean=mean, rstd=rstd, family="gn16")
+        assert f, (fault, name)
+        if fault in ("drop_row", "next_group_chunk", "affine_shift", "rtz"):
+            assert any("outside the bound" in m for m in f), f
+        if fault in ("drop_row", "n_minus_1", "eps_outside"):
+            assert any("outside the bound (worst" in m and ("means" in m or "rstd" in m) for m in f), f
+        if fault == "rtz" and em["x"].numel() >= 5 * X.MIN_DIRECTION_ELEMS:
+            assert any("direction" in m for m in f), f
+        if fault == "drop_row" and "4097" in name:          # ... where the old criterion has nothing to see
+            assert _rel_l2(out, em["ref"][0]["y"].reshape(out.shape)) <= (4e-3 if dt == torch.bfloat16 else 5e-4)      # test_gpu_ops.py's bounds
+
+
+LN_EMU = [(320, 33), (768, 17), (2048, 9)]
+
+
+@pytest.mark.parametrize("dt", DTYPES, ids=["bf16", "f16"])
+def test_layernorm_emulation_passes_and_planted_faults_are_found(dt):
+    """k_layernorm / adaLN / k_row_stats in fp32 with the lane-strided sums and the butterfly: inside the bound; the n - 1 variance,
+    eps outside the root, gamma / beta one channel off, the next sample's scale on a sample's last row and truncating stores are not."""
+    for Cc, rows in LN_EMU:
+        x = NC.ln_input(rows, Cc, dt, seed=rows)
+        gamma, beta = NC.affine(Cc, seed=1)
+        ref = X.norm_reference(x.double(), gamma.double(), beta.double(), (1,), 1e-5, e2=False, family="ln16")
+        ref32 = torch.nn.functional.layer_norm(x.float(), (Cc,), gamma, beta, 1e-5)
+        out, mean, rstd = NC.emulate_ln16(x, gamma, beta, 1e-5, dt)
+        assert _norm_verdict(out, ref, dt, mean=mean, rstd=rstd, family="ln16", ref32=ref32) == [], Cc
+        assert X.clean_share(ref, dt) >= X.CLEAN_SHARE_MIN
+        for fault in ("n_minus_1", "eps_outside", "affine_shift", "rtz"):
+            out, mean, rstd = NC.emulate_ln16(x, gamma, beta, 1e-5, dt, fault=fault)
+            assert _norm_verdict(out, ref, dt, mean=mean, rstd=rstd, family="ln16", ref32=ref32), (Cc, fault)
+        rpb = 5
+        mod = NC.mod_input((rows + rpb - 1) // rpb, Cc, seed=rpb)
+        g, b = NC.mod_rows(mod, Cc, rows, rpb)
+        refm = X.norm_reference(x.double(), g, b, (1,), 1e-6, e2=False, family="ln16mod")
+        b_of = torch.arange(rows) // rpb
+        scale, shift = mod[b_of, Cc:2 * Cc], mod[b_of, :Cc]
+        assert _norm_verdict(NC.emulate_ln16(x, scale, shift, 1e-6, dt, mod=True)[0], refm, dt) == [], Cc
+        if rows > rpb:
+            bad = NC.emulate_ln16(x, scale, shift, 1e-6, dt, mod=True, fault="next_sample_scale", rows_per_batch=rpb)[0]
+            f = _norm_verdict(bad, refm, dt)
+            assert len(f) == 1 and "outside the bound" in f[0], f
+
+
+def test_f32_form_emulations_pass_the_criterion():
+    """The f32 forms: double statistics rounded once (GroupNorm), lane-strided f32 sums (LayerNorm, adaLN); f32 outputs have no
+    16-bit rounding to hide behind, so the bound is 1/2 ulp_f32 + ARITH S + STAT Q alone."""
+    c = NC.GNF32_ROWS_CASES["rows: hw 17, 320 + 640"]
+    x = NC.gn_input(2, c["hw"], c["C"], torch.float32, seed=4)
+    gamma, beta = NC.affine(c["C"])
+    for silu in (0, 1):
+        ref = _gn_ref(x, c["G"], gamma, beta, 1e-5, silu, family="gnf32")
+        assert _norm_verdict(NC.emulate_gnf32(x, c["G"], 1e-5, gamma, beta, silu), ref, torch.float32) == []
+    for Cc in (77, 260, 1538):
+        x = NC.ln_input(9, Cc, torch.float32, seed=Cc)
+        gamma, beta = NC.affine(Cc, seed=2)
+        ref = X.norm_reference(x.double(), gamma.double(), beta.double(), (1,), 1e-5, e2=False, family="lnf32")
+        assert _norm_verdict(NC.emulate_lnf32(x, gamma, beta, 1e-5), ref, torch.float32) == [], Cc
+        bad = NC.emulate_lnf32(x, torch.roll(gamma, 1), beta, 1e-5)
+        assert _norm_verdict(bad, ref, torch.float32), Cc

@@ -76,6 +76,57 @@ function of the split operands, so the kernels are held to ACCUMULATION error, n
   3e-5 rel-L2 bounds of tests/test_gpu_f32.py and tests/test_gpu_x3t.py rest on it.
   Clamped loads: k_gemm_x3 fetches rows past M / N from the last valid row instead of predicating, so its A and W operands live
   in exact-size allocations bracketed by NaN rows (bracketed): one row past the clamp poisons a checked value.
+
+Normalisation kernels (GroupNorm, LayerNorm, adaLN, row statistics; tests/test_gpu_norm_exact.py).  y = (x - mu) r g + b with
+mu, v the exact population mean / variance of the normalised set, r = (v + eps)^-1/2, g = gamma (1 + scale for adaLN), b = beta
+(shift), all in float64 on the 16-bit or f32 values the kernel reads.  For every element
+
+    |out - f(y)| <= 1/2 ulp_T(f(y)) + ARITH S + STAT Q          (f = identity or SiLU, carried as apply_act(..., 1) does)
+    S = |g| r (|x| + |mu|) + |b|
+    Q = |g| r (m1 + |x - mu| M2 / (2 (v + eps)))
+
+  m1      mean |x| over the set: a statistics error of STAT m1 in the mean moves y by |g| r STAT m1.
+  M2      mean x^2 over the set for the kernels that form E[x^2] - mean^2 (both statistic sources of the 16-bit GroupNorm, the
+          three f32 GroupNorm forms), v for the kernels that sum centred squares (every LayerNorm form, k_row_stats): an error
+          of STAT M2 in the variance moves r by r STAT M2 / (2 (v + eps)).  Q therefore GROWS with M2 / v = 1 + (mean / std)^2:
+          that is the price of the one-pass variance, and the cancellation cases put a number on it.
+  ARITH   derived, NORM_ARITH[family] = (fp32 roundings between the statistics and the stored value) x 2^-24, each rounding taken
+          as <= 2^-24 S and rsqrtf / (1 / sqrt) as 2 of them:
+            gn16     k_gn_apply: a = rstd gamma, mean a, beta - mean a, fmaf(x, a, cb): 4, + rsqrtf 2               = 6
+            ln16     k_layernorm: x - mean, . rstd, . gamma, + beta: 4, + rsqrtf 2                                   = 6
+            ln16mod  the same with 1 + scale formed first: 5, + rsqrtf 2                                             = 7
+            gnf32    k_gn_rows_apply / k_groupnorm_f32 / _any: x - mean, . rstd, . gamma, + beta: 4; (float) mean and
+                     (float)(1 / sqrt(double)) one rounding each                                                     = 6
+            lnf32    k_layernorm_f32_regs / k_layernorm_f32: 4, + 1.0f / sqrtf 2                                     = 6
+            lnf32mod k_layernorm_mod_f32: 5, + 1.0f / sqrtf 2                                                        = 7
+          None needs more than 8 (2^-21).  SiLU adds apply_act's GELU_D and ACT_REL |y| on top, as in the GEMM epilogues.
+  STAT    measured per family against the float64 statistics -- on stats_ws[b][g] = (mean, rstd) after sdn_groupnorm_* /
+          sdn_groupnorm_cols_*, on the output of sdn_row_stats_* (the reduction code of k_layernorm), and for the f32 forms, which
+          expose no statistics, on their f32 outputs (what of |out - y| is left after 1/2 ulp + ARITH S, per unit of Q) -- as the
+          worst |mean_out - mu| / m1 and |rstd_out - r| / (r M2 / (2 (v + eps))) over the cases; the constant is 4x that worst
+          (the margin of X3_ACC), and must stay below the hard bound (family's longest serial fp32 chain) x 2^-24:
+            family      measured worst (MI355X, profiles/norm_exact.json)          constant      longest chain -> hard bound
+            gn16        0.507 x 2^-20  rstd, |mean| / std 100 at hw 4097 (fp16)     2.03 x 2^-20  268 (C 1928, G 8: 241 + 17 + ...)  2^-15.9
+            gn16serial  3.913 x 2^-20  rstd, hw 100, C 64, G 1 (bf16)               15.65 x 2^-20 2059 (rt x cpg = 32 x 64 = 2048)   2^-13.0
+            gn16cols    0.238 x 2^-20  rstd, hw 384, 320 + 640 (fp16)               0.95 x 2^-20  140 (128 rows per partial + 12)    2^-16.9
+            ln16        0.426 x 2^-20  rstd, C 1536 with a common offset of 40      1.70 x 2^-20  39 (4 x 8 + 6 + 1)                 2^-18.7
+            gnf32       0  (every f32 output within 1/2 ulp + ARITH S)              2^-24         2 (mean, rstd rounded once each)   2^-23
+            lnf32       0.001 x 2^-20  k_layernorm_mod_f32, C 1024                  2^-24         39 (C 1538 / 64 + 6 + 1 ...)       2^-18.7
+          mean errors are far smaller throughout (<= 0.174 x 2^-20 m1).  The two f32 families measure nothing above a single
+          rounding, so their constant is floored at the 2^-24 of rounding a statistic to f32.  gn16serial is ONE shape: k_gn_stats
+          lets one thread per group add the group's rt x cpg LDS partials in a serial chain, 2048 terms at C = 64, G = 1 against
+          <= 241 for every other tested shape and <= 80 for the shapes the models run; its statistics are 7x less accurate -- inside
+          the hard bound, so a constant and not a bug by this criterion's own rule, but recorded as a finding (norm_cases.GN16_CASES).
+          A value above the hard bound is a bug to find, not a constant to raise.
+  The statistics themselves are asserted: |mean_out - mu| <= 1/2 ulp_f32(mu) + STAT m1 and |rstd_out - r| <= 1/2 ulp_f32(r) +
+  STAT r M2 / (2 (v + eps)) (rsqrtf's own error is part of what STAT measures; where M2 / (2 (v + eps)) < 1/4 -- an all-zero group of
+  a probe input -- the term is floored at rsqrtf's 2 ulp, 2^-22 r, which it would otherwise leave no room for).  Triple outputs (*_f32_triple) are held to bit equality with the split of the
+  checked f32 output of the same inputs (check_split_planes).
+  Clean share: in every case not named a cancellation case at least 98 % of the elements have ARITH S + STAT Q <= 1/4 ulp_T(y),
+  i.e. the storage rounding decides -- the bound is not hiding a failure behind its own slack (16-bit outputs only; for f32
+  outputs the constants' distance to the hard bounds is the control).
+  Clamped loads: k_layernorm, k_row_stats and k_gn_stats fetch tail rows from the last valid row, so their inputs carry NaN rows
+  right behind the valid extent (with_nan_tail): one row past the clamp poisons a checked value.
 """
 import math
 
@@ -423,3 +474,103 @@ def check_split_planes(out16, f, planes):
     if planes == 3 and not torch.equal(bits(out16[:, 2]), bits(out16[:, 0])):
         bad.append(f"third plane differs from hi in {int((bits(out16[:, 2]) != bits(out16[:, 0])).sum())} elements")
     return bad
+
+
+# ---- the normalisation kernels (tests/test_gpu_norm_exact.py; docstring above: "Normalisation kernels") -----------------------------
+NORM_ARITH = {"gn16": 6 * 2.0 ** -24, "gn16serial": 6 * 2.0 ** -24, "gn16cols": 6 * 2.0 ** -24, "ln16": 6 * 2.0 ** -24, "ln16mod": 7 * 2.0 ** -24, "gnf32": 6 * 2.0 ** -24, "lnf32": 6 * 2.0 ** -24,
+              "lnf32mod": 7 * 2.0 ** -24}
+# Statistics constant per family, 4x the measured worst (profiles/norm_exact.json); NORM_STAT_CHAIN: the longest serial fp32 chain
+# of the family's statistics over the tested shapes (norm_cases.gn16_chain / ln16_chain restate the code), whose 2^-24 multiple is
+# the hard bound the constant must stay below.
+NORM_STAT = {"gn16": 4 * 0.507 * ACC, "gn16serial": 4 * 3.913 * ACC, "gn16cols": 4 * 0.238 * ACC, "ln16": 4 * 0.426 * ACC,
+             "gnf32": 2.0 ** -24, "lnf32": 2.0 ** -24}
+NORM_STAT_FAMILY = {"gn16": "gn16", "gn16serial": "gn16serial", "gn16cols": "gn16cols", "ln16": "ln16", "ln16mod": "ln16", "gnf32": "gnf32", "lnf32": "lnf32",
+                    "lnf32mod": "lnf32"}
+CLEAN_SHARE_MIN = 0.98
+
+# What the launchers of sdn_norm.hip and sdn_f32.hip can launch (tests/test_exact_checker.py parses them), as
+# (name, NQ or NV, R): the key sdn_debug_norm_last_launch's record maps to (norm_launch_key).
+NORM_KERNEL = {1: "gn_stats", 2: "gn_cols", 3: "layernorm", 4: "layernorm_mod", 5: "row_stats", 6: "gn_f32_rows", 7: "gn_f32_pairs",
+               8: "gn_f32_any", 9: "ln_f32_regs", 10: "ln_f32", 11: "ln_mod_f32"}
+NORM_INSTANTIATIONS = (
+    [("gn_stats", 0, 0), ("gn_cols", 0, 0)]
+    + [(k, nq, r) for k in ("layernorm", "layernorm_mod", "row_stats") for nq, r in ((1, 4), (2, 2), (4, 1))]
+    + [("gn_f32_rows", 0, 0), ("gn_f32_pairs", 0, 0), ("gn_f32_any", 0, 0), ("ln_f32_regs", 0, 0), ("ln_f32", 0, 0)]
+    + [("ln_mod_f32", nv, 0) for nv in (2, 4, 8)])
+NORM_16BIT = {"gn_stats", "gn_cols", "layernorm", "layernorm_mod", "row_stats"}       # run in bf16 and fp16; the others in f32
+NORM_TRIPLE = {"gn_f32_rows", "gn_f32_pairs", "gn_f32_any", "ln_f32_regs", "ln_f32"}   # have a *_f32_triple entry point
+NL_FIELDS = ("kernel", "dtype", "nq", "r", "nch", "ct", "ntiles", "rows_per_tile", "rpc", "nchunk", "stats_src", "triple")
+
+
+def norm_launch_key(rec) -> tuple:
+    """sdn_debug_norm_last_launch's record -> the NORM_INSTANTIATIONS key it ran."""
+    return (NORM_KERNEL[rec[0]], rec[2], rec[3])
+
+
+def norm_coverage_wanted() -> set:
+    """(key, dtype code, triple) of everything the norm launchers can run: 16-bit kernels in bf16 (0) and fp16 (1), f32 ones (2)
+    plain and, where the entry point exists, triple."""
+    want = set()
+    for k in NORM_INSTANTIATIONS:
+        if k[0] in NORM_16BIT:
+            want |= {(k, 0, 0), (k, 1, 0)}
+        else:
+            want |= {(k, 2, 0)} | ({(k, 2, 1)} if k[0] in NORM_TRIPLE else set())
+    return want
+
+
+def norm_reference(x, g, b, dims, eps, *, e2, family, act=0, stat=None):
+    """Float64 reference of y = (x - mu) r g + b over the sets spanned by `dims` of x (g, b broadcastable to x).
+    e2: the kernel forms E[x^2] - mean^2 (M2 = mean x^2) rather than centred squares (M2 = v).
+    Returns dict(y, s, e, pre_y, pre_budget, mu, r, m1, k2, S, Q): s = (ARITH S + STAT Q) / ACC for analyse(), carried through the
+    activation; pre_y / pre_budget = y and ARITH S + STAT Q before the activation (the clean share's terms); k2 = M2 / (2 (v + eps))."""
+    x, g, b = x.to(F64), g.to(F64), b.to(F64)
+    eps = float(torch.tensor(eps, dtype=torch.float32))       # the kernels take eps as a float
+    arith = NORM_ARITH[family]
+    stat = NORM_STAT[NORM_STAT_FAMILY[family]] if stat is None else stat
+    mu = x.mean(dims, keepdim=True)
+    v = ((x - mu) ** 2).mean(dims, keepdim=True)
+    r = (v + eps) ** -0.5
+    m1 = x.abs().mean(dims, keepdim=True)
+    k2 = ((x * x).mean(dims, keepdim=True) if e2 else v) / (2 * (v + eps))
+    y = (x - mu) * r * g + b
+    S = g.abs() * r * (x.abs() + mu.abs()) + b.abs()
+    Q = g.abs() * r * (m1 + (x - mu).abs() * k2)
+    pre_y = y
+    y, s, e = apply_act(y, (arith * S + stat * Q) / ACC, act)
+    return dict(y=y, s=s, e=e, pre_y=pre_y, pre_budget=arith * S + stat * Q, mu=mu, r=r, m1=m1, k2=k2, S=S, Q=Q)
+
+
+def clean_share(ref, dtype) -> float:
+    """Fraction of the elements with ARITH S + STAT Q <= 1/4 ulp_T(y), y = (x - mu) r g + b: where the storage rounding decides."""
+    return float((ref["pre_budget"] <= 0.25 * ulp(ref["pre_y"], dtype)).double().mean())
+
+
+def stat_errors(mean_out, rstd_out, ref) -> dict:
+    """Statistics a kernel exposed (f32) against the reference's, in the units STAT is measured in: the worst |mean_out - mu| / m1
+    and |rstd_out - r| / (r k2).  Sets with k2 < 1/4 (v + eps dominated by eps: an all-zero group, a set of one zero) are left out
+    of the rstd figure: there the variance carries no error to measure and what is left is rsqrtf's own (stat_failures)."""
+    mu, r, m1, k2 = (ref[k].reshape(mean_out.shape) for k in ("mu", "r", "m1", "k2"))
+    dm, dr = (mean_out.to(F64) - mu).abs(), (rstd_out.to(F64) - r).abs()
+    rel_m = torch.where(m1 > 0, dm / m1.clamp_min(1e-300), torch.zeros_like(dm))
+    rel_r = torch.where(k2 >= 0.25, dr / (r * k2.clamp_min(0.25)), torch.zeros_like(dr))
+    return dict(mean_err=float(rel_m.max()), rstd_err=float(rel_r.max()), dm=dm, dr=dr, mu=mu, r=r, m1=m1, k2=k2)
+
+
+RSQRT_REL = 2.0 ** -22            # rsqrtf / 1 / sqrt: <= 2 ulp, the figure ARITH uses
+
+
+def stat_failures(se, stat) -> list:
+    """Sets outside |mean_out - mu| <= 1/2 ulp_f32(mu) + STAT m1 or |rstd_out - r| <= 1/2 ulp_f32(r) + max(STAT k2, RSQRT_REL) r.
+    The floor RSQRT_REL only acts where k2 < RSQRT_REL / STAT (<= 1/4 for STAT >= 2^-20), i.e. where eps dominates v + eps and
+    the formula's M2 / (2 (v + eps)) would leave the reciprocal square root's own 2 ulp no room at all."""
+    f = []
+    bad_m = se["dm"] > 0.5 * ulp(se["mu"], torch.float32) + stat * se["m1"]
+    bad_r = se["dr"] > 0.5 * ulp(se["r"], torch.float32) + torch.clamp(stat * se["k2"], min=RSQRT_REL) * se["r"]
+    if bool(bad_m.any()):
+        f.append(f"{int(bad_m.sum())} means outside the bound (worst {se['mean_err']:.3g} m1)")
+    if bool(bad_r.any()):
+        f.append(f"{int(bad_r.sum())} rstd outside the bound (worst {se['rstd_err']:.3g} r M2 / (2 (v + eps)))")
+    if bool(torch.isnan(se["dm"]).any() | torch.isnan(se["dr"]).any()):
+        f.append("NaN statistics")
+    return f

@@ -80,27 +80,79 @@ def gemm(a, w, *, bias=None, rowbias=None, residual=None, a2=None, conv=None, ac
     return out
 
 
-def groupnorm(x, x2, groups, eps, silu, gamma, beta, cols1=None, cols2=None):
+def gn_workspace(B, groups, device):
+    """Scratch of the GroupNorm entry points: (mean, rstd) per (sample, group) first, then up to 128 tiles of partials."""
+    return torch.empty(B * 129 * groups * 2, dtype=torch.float32, device=device)
+
+
+def groupnorm(x, x2, groups, eps, silu, gamma, beta, cols1=None, cols2=None, out=None, ws=None, check=True):
+    """out / ws: caller-owned output [B, hw, C] and workspace (e.g. views into guarded buffers).  check=False returns the status
+    code instead of raising on it."""
     B, hw, c1 = x.shape
     c2 = 0 if x2 is None else x2.shape[2]
-    out = torch.empty((B, hw, c1 + c2), dtype=x.dtype, device=x.device)
-    ws = torch.empty(B * 129 * groups * 2, dtype=torch.float32, device=x.device)
+    out = torch.empty((B, hw, c1 + c2), dtype=x.dtype, device=x.device) if out is None else out
+    ws = gn_workspace(B, groups, x.device) if ws is None else ws
     if cols1 is not None:
-        _lib.check(_fn("groupnorm_cols", x)(x.data_ptr(), None if x2 is None else x2.data_ptr(), B, hw, c1, c2, groups, eps, silu,
-                                                     gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), ws.data_ptr(), cols1.data_ptr(),
-                                                     None if cols2 is None else cols2.data_ptr(), _lib.stream_ptr()), "sdn_groupnorm_cols")
-        return out
-    _lib.check(_fn("groupnorm", x)(x.data_ptr(), None if x2 is None else x2.data_ptr(), B, hw, c1, c2, groups,
-                                            eps, silu, gamma.data_ptr(), beta.data_ptr(), out.data_ptr(),
-                                            ws.data_ptr(), _lib.stream_ptr()), "sdn_groupnorm_bf16")
+        rc = _fn("groupnorm_cols", x)(x.data_ptr(), None if x2 is None else x2.data_ptr(), B, hw, c1, c2, groups, eps, silu,
+                                      gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), ws.data_ptr(), cols1.data_ptr(),
+                                      None if cols2 is None else cols2.data_ptr(), _lib.stream_ptr())
+    else:
+        rc = _fn("groupnorm", x)(x.data_ptr(), None if x2 is None else x2.data_ptr(), B, hw, c1, c2, groups,
+                                 eps, silu, gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), ws.data_ptr(), _lib.stream_ptr())
+    if not check:
+        return rc
+    _lib.check(rc, "sdn_groupnorm")
     return out
 
 
-def layernorm(x, gamma, beta, eps=1e-5):
+def groupnorm_f32(x, x2, groups, eps, silu, gamma, beta, *, out, ws=None, triple=False, check=True):
+    """sdn_groupnorm_f32 / _f32_triple on f32 maps; ws=None passes stats_ws = NULL (the per-group kernels).  out: f32 [B, hw, C]
+    or the bf16 triple [B, hw, 3, C]."""
+    B, hw, c1 = x.shape
+    c2 = 0 if x2 is None else x2.shape[2]
+    fn = sda.lib().sdn_groupnorm_f32_triple if triple else sda.lib().sdn_groupnorm_f32
+    rc = fn(x.data_ptr(), None if x2 is None else x2.data_ptr(), B, hw, c1, c2, groups, eps, silu, gamma.data_ptr(), beta.data_ptr(),
+            out.data_ptr(), None if ws is None else ws.data_ptr(), _lib.stream_ptr())
+    if not check:
+        return rc
+    _lib.check(rc, "sdn_groupnorm_f32")
+    return out
+
+
+def layernorm(x, gamma, beta, eps=1e-5, out=None, triple=False, check=True):
+    """triple (f32 x only): sdn_layernorm_f32_triple into a caller-owned bf16 [rows, 3, c]."""
     rows, c = x.shape
-    out = torch.empty_like(x)
-    _lib.check(_fn("layernorm", x)(x.data_ptr(), rows, c, eps, gamma.data_ptr(), beta.data_ptr(),
-                                            out.data_ptr(), _lib.stream_ptr()), "sdn_layernorm_bf16")
+    out = torch.empty_like(x) if out is None else out
+    fn = sda.lib().sdn_layernorm_f32_triple if triple else _fn("layernorm", x)
+    rc = fn(x.data_ptr(), rows, c, eps, gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), _lib.stream_ptr())
+    if not check:
+        return rc
+    _lib.check(rc, "sdn_layernorm")
+    return out
+
+
+def layernorm_mod(x, scale, shift, rows_per_batch, eps=1e-6, out=None, check=True):
+    """adaLN: LN(x) * (1 + scale[b]) + shift[b]; scale / shift [nb, c] f32, column slices of one stacked tensor allowed (their
+    common row stride is ld_mod)."""
+    rows, c = x.shape
+    assert scale.stride(0) == shift.stride(0) and scale.stride(1) == 1 and shift.stride(1) == 1
+    out = torch.empty_like(x) if out is None else out
+    rc = _fn("layernorm_mod", x)(x.data_ptr(), rows, c, eps, scale.data_ptr(), shift.data_ptr(), scale.stride(0), rows_per_batch,
+                                 out.data_ptr(), _lib.stream_ptr())
+    if not check:
+        return rc
+    _lib.check(rc, "sdn_layernorm_mod")
+    return out
+
+
+def row_stats(x, eps=1e-5, out=None, check=True):
+    """(mean, rstd) per row of a 16-bit x [rows, c] -> f32 [rows, 2]."""
+    rows, c = x.shape
+    out = torch.empty(rows, 2, dtype=torch.float32, device=x.device) if out is None else out
+    rc = _fn("row_stats", x)(x.data_ptr(), rows, c, eps, out.data_ptr(), _lib.stream_ptr())
+    if not check:
+        return rc
+    _lib.check(rc, "sdn_row_stats")
     return out
 
 
