@@ -202,7 +202,13 @@ typedef struct sdn_gemm_desc {
                                0 or K = single source                                         */
   int32_t Hs, Ws, Cin;      /* CONV3X3: stored input map [B,Hs,Ws,Cin], K = 9*Cin             */
   int32_t Ho, Wo, stride;   /*          output map, stride 1|2 (Downsample2D)                  */
-  int32_t upsample;         /*          1 = nearest-2x of the stored map first (Upsample2D)    */
+  int32_t upsample;         /*          1 = nearest-2x of the stored map first (Upsample2D)
+                                        2 = the same operator in PHASE form (sdn_gemm_bf16 / _f16 and sdn_gemm_stats_* only): per output
+                                        parity (py, px) a 2x2 conv over the STORED map, K = 4*Cin, `w` = the four [N, 4*Cin] matrices
+                                        of sdn_conv_up4_weights.  Hs*Ws % 256 == 0, Ws >= 8, N % 320 == 0 or N % 256 == 0; bias and
+                                        column statistics only, whole-width 16-bit output; Ho = 2 Hs, Wo = 2 Ws, stride 1.  The
+                                        statistics blocks follow the GEMM's row order (sample, phase, low-res pixel): 128-row blocks
+                                        of ONE sample each, 4 Hs Ws / 128 per sample, as sdn_groupnorm_cols_* sums them        */
   int32_t act;              /* SDN_ACT_*                                                       */
   int32_t out_kind;         /* SDN_OUT_*                                                       */
   int32_t rows_per_batch;   /* rows of one sample (H*W): row -> sample for rowbias / NCHW      */
@@ -563,6 +569,14 @@ int sdn_gemm_splitk_f16(const sdn_gemm_desc* d, const void* a, const void* a2, c
                         const float* rowbias, const float* rowgate, const void* residual, void* out, void* partials,
                         size_t partial_bytes, void* stream);
 
+/* Phase weights of an upsampler conv (Upsample2D: nearest-2x, then conv3x3), for sdn_gemm_desc.upsample = 2.  After nearest
+ * upsampling the nine taps of output pixel (2y + py, 2x + px) read only the 2 x 2 stored pixels (y + a - 1 + py, x + b - 1 + px),
+ * a, b in {0, 1}: row a collects ty {0} | {1, 2} (py = 0) or {0, 1} | {2} (py = 1), and the same in x.  w9 = the packed
+ * SDN_P_CONV3X3 matrix [N][9 Cin] (k = (3 ty + tx) Cin + c); out [4][N][4 Cin], phase 2 py + px, k = (2 a + b) Cin + c, each
+ * element the fp32 sum (ty-major, tx-minor) of its 1, 2 or 4 stored taps, rounded once to the storage type (0 = bf16, 1 = fp16).
+ * Once per weight set (sdn_unet_prepare does it for the plans that use the form). */
+int sdn_conv_up4_weights(int32_t dtype, const void* w9, int32_t N, int32_t Cin, void* out, void* stream);
+
 /* out[k * bytes + i] = in[i], k < rep (device-side `torch.cat([x] * rep)`; bytes % 16 == 0) */
 int sdn_repeat(const void* in, size_t bytes, int32_t rep, void* out, void* stream);
 
@@ -851,6 +865,14 @@ void sdn_unet_set_graph_mode(sdn_unet* u, int32_t on);
  * order then depends on the batch size (without it a sample's output is bit-identical at every batch size).  Changing it
  * rebuilds the plans: query sdn_unet_workspace_bytes again. */
 void sdn_unet_set_split_k(sdn_unet* u, int32_t on);
+/* Upsampler convs of the 16-bit UNet plans in phase form (sdn_gemm_desc.upsample = 2 over the weights of sdn_conv_up4_weights:
+ * 4/9 of the nine-tap matrix work) where the shape qualifies -- a stored map of Hs Ws % 256 == 0 pixels, Cin % 64 == 0, N % 320 == 0
+ * or N % 256 == 0: SD-v1.4's 16^2 -> 32^2 and 32^2 -> 64^2 levels.  On by default; 0 selects the nine-tap op everywhere (A/B, tests).
+ * The choice never depends on the batch, so a sample keeps its bits at every batch size; outputs differ from the nine-tap form by
+ * one more rounding of the summed weights.  The derived weight regions stay in the manifest either way (they are its last
+ * entries, 16 N Cin elements per qualifying upsampler: 66 MB for SD-v1.4, part of sdn_unet_weight_bytes and filled by
+ * sdn_unet_prepare even when the switch is off, so that the packed buffer never depends on it); changing the switch rebuilds the plans.  No effect on fp32-storage plans and on handles that are not a UNet. */
+void sdn_unet_set_conv_up4(sdn_unet* u, int32_t on);
 
 /* ---- opt-in measurement: HIP events around every launch of ONE forward, on the forward's own stream ---- */
 typedef struct sdn_profile_row {

@@ -222,6 +222,8 @@ SIGNATURES = {
     "sdn_unet_set_graph_mode": (None, [_vp, _i32]),
     "sdn_unet_set_text_version": (None, [_vp, C.c_uint64]),
     "sdn_unet_set_split_k": (None, [_vp, _i32]),
+    "sdn_unet_set_conv_up4": (None, [_vp, _i32]),
+    "sdn_conv_up4_weights": (C.c_int, [_i32, _vp, _i32, _i32, _vp, _vp]),
     "sdn_unet_profile_next": (None, [_vp]),
     "sdn_unet_profile_read": (C.c_int, [_vp, C.POINTER(ProfileRow), _i32]),
 }

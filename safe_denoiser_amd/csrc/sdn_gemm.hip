@@ -48,7 +48,12 @@ namespace sdn_gemm_detail {
 // written by a read-only pre-pass (sdn_row_stats_*), for wide N.
 // (H8 = the experimental operand form of DESIGN 10.12; it lives in its OWN kernel symbol, k_gemm_h8, so that the production
 //  instances keep their code and registers -- sharing one body cost the fp16 instances 600 spilled registers)
-template <typename T, int NREP, int WGM, int NSTAGE, int LNF, bool H8>
+// UP4 = the phase form of a 3x3 conv over a nearest-2x upsampled map (sdn_gemm_desc.upsample = 2): for each output
+// parity (py, px) the nine taps read only 2 x 2 stored pixels, so the op is four 2x2 convs over the STORED map with summed tap
+// weights (sdn_conv_up4_weights), K = 4 Cin instead of 9 Cin.  GEMM rows go sample, phase, low-res pixel (m = b 4hw + p hw + q, hw a
+// multiple of the tile's rows: one sample and one phase per tile); the staged epilogue scatters whole rows to (2y + py, 2x + px).
+// Like H8 it is a compile-time flag with its own kernel symbol, k_gemm_up4: the production instances keep their code and registers.
+template <typename T, int NREP, int WGM, int NSTAGE, int LNF, bool H8, bool UP4 = false>
 __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g) {
 #if defined(__HIP_DEVICE_COMPILE__)
   SDN_STAMP(0)
@@ -106,7 +111,29 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g) {
   // (this setup runs before the first DMA can be issued -- in-kernel stamps put it at 2-7 k cycles, 4-11 % of a tile -- so
   //  it is kept short: the pieces of a lane are rows m, m+8, m+16, ...: ONE division pair, then increments; the 9-tap halo
   //  mask is an outer product of 3 row bits and 3 column bits)
-  if (g.a_mode == 1) {
+  // UP4: all the k loop and the epilogue keep of the tile's (sample, phase) -- three wave-uniform values
+  [[maybe_unused]] int up_d0 = 0, up_m0 = 0, up_out0 = 0;   // byte delta of tap (0, 0); first GEMM row of the (sample, phase); output row of its pixel (0, 0)
+  if constexpr (UP4) {
+    // a_base = the low-res pixel q = (y, x) itself; tap (a, b) of phase (py, px) reads (y + a - 1 + py, x + b - 1 + px): a delta that
+    // is uniform over the tile.  Bits 0-3 of a_base (a multiple of 16 otherwise) = tap 2a + b lies inside the stored map: the mode
+    // keeps no a_aux registers.
+    const int hw = g.Hs * g.Ws;
+    const int sp = m0 / hw;                                  // 4 b + p
+    const int py = (sp >> 1) & 1, px = sp & 1;
+    up_d0 = (((py - 1) * g.Ws + (px - 1)) * g.Cin) * 2;
+    up_m0 = sp * hw;
+    up_out0 = (sp >> 2) * 4 * hw + py * 2 * g.Ws + px;
+    const int q = m0 - up_m0 + wid * A_PIECES * 8 + lrow;
+    int y = q / g.Ws, x = q - y * g.Ws;
+#pragma unroll
+    for (int i = 0; i < A_PIECES; ++i) {
+      if (i > 0) { x += 8; if (x >= g.Ws) { x -= g.Ws; ++y; } }          // (host: Ws >= 8)
+      const unsigned rb = ((y + py >= 1) ? 1u : 0u) | ((y + py < g.Hs) ? 2u : 0u);
+      const unsigned cb = ((x + px >= 1) ? 1u : 0u) | ((x + px < g.Ws) ? 2u : 0u);
+      a_aux[i] = 0u;
+      a_base[i] = (unsigned)(((((sp >> 2) * g.Hs + y) * g.Ws + x) * g.Cin + lchunk * 8) * 2) | ((rb & 1u) ? cb : 0u) | ((rb & 2u) ? cb << 2 : 0u);
+    }
+  } else if (g.a_mode == 1) {
     const int hw = g.Ho * g.Wo;
     const int Hi = g.upsample ? g.Hs * 2 : g.Hs, Wi = g.upsample ? g.Ws * 2 : g.Ws;
     const int mb = m0 + wid * A_PIECES * 8 + lrow;
@@ -155,8 +182,9 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g) {
     const int piece = wid * W_PIECES + i;
     w_ok[i] = piece * 8 < BN;
     w_off[i] = (unsigned)(((long)(n0 + piece * 8 + lrow) * g.K + lchunk * 8) * 2);
+    if constexpr (UP4) w_off[i] += (unsigned)((long)((m0 / (g.Hs * g.Ws)) & 3) * g.N * g.K * 2);     // this phase's [N][4 Cin] matrix
   }
-  const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(g.w, (unsigned)((long)g.N * g.K * 2));
+  const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(g.w, (unsigned)((long)g.N * g.K * 2 * (UP4 ? 4 : 1)));
   const long a_rows = g.a_mode == 1 ? (long)(g.M / (g.Ho * g.Wo)) * g.Hs * g.Ws : (long)g.M;
   const __amdgpu_buffer_rsrc_t rs_a1 = make_rsrc(g.a, (unsigned)(a_rows * ld1 * 2));
   const __amdgpu_buffer_rsrc_t rs_a2 = make_rsrc(g.a2 ? g.a2 : g.a, (unsigned)(g.a2 ? a_rows * ld2 * 2 : 0));
@@ -168,7 +196,18 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g) {
   auto issue_aw = [&](int buf, bool with_w) {
     unsigned char* sa = smem + buf * STAGE;
     unsigned char* sw = sa + BM * 128;
-    if (g.a_mode == 1) {
+    if constexpr (UP4) {                            // k order = channel chunk outer, the four taps (tap = 2a + b) inner
+      // (tap and chunk come from the k-tile index: a cursor pair kept beside cur_k0 ended up in scratch -- the two "+= BK" updates
+      //  were merged into one store through a selected address, which kept all three cursors in memory)
+      const int tap = (cur_k0 >> 6) & 3, c0 = (cur_k0 >> 8) << 6;
+      const int delta = up_d0 + (((tap >> 1) * g.Ws + (tap & 1)) * g.Cin + c0) * 2;       // wave-uniform
+#pragma unroll
+      for (int i = 0; i < A_PIECES; ++i) {
+        const unsigned off = ((a_base[i] >> tap) & 1u) ? (a_base[i] & ~15u) + (unsigned)delta : OOB;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a1, (lds_ptr_t)(sa + (wid * A_PIECES + i) * 1024), 16, off, 0, 0, 0);
+      }
+      w_k0 = tap * g.Cin + c0;
+    } else if (g.a_mode == 1) {
       const int dy = cur_ty - 1, dx = cur_tx - 1, tap = cur_ty * 3 + cur_tx;
       if (!g.upsample) {
         const int delta = ((dy * g.Ws + dx) * g.Cin + cur_c0) * 2;                    // wave-uniform
@@ -504,6 +543,17 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g) {
   constexpr int WM_PER_PASS = WGM / PASSES, ROWS_PER_PASS = 64 * WM_PER_PASS;
   static_assert(WGM % PASSES == 0, "pass split must divide the wave rows");
   static_assert(PASSES <= 2, "epilogue is written for at most two staging passes");
+  // UP4: GEMM row m = low-res pixel (y, x) of the tile's sample and phase -> row (2y + py) 2Ws + 2x + px of that sample's map
+  [[maybe_unused]] auto epi_out_row = [&](int m) -> int {
+    if constexpr (UP4) {
+      const int q = m - up_m0;
+      const int y = q / g.Ws, x = q - y * g.Ws;
+      return up_out0 + 4 * g.Ws * y + 2 * x;
+    } else {
+      return m;
+    }
+  };
+#define SDN_EPI_OUT_ROW(m) epi_out_row(m)
 #define SDN_PASS 0
 #include "sdn_gemm_epilogue.inc"
 #undef SDN_PASS
@@ -512,6 +562,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& g) {
 #include "sdn_gemm_epilogue.inc"
 #undef SDN_PASS
   }
+#undef SDN_EPI_OUT_ROW
   SDN_STAMP(3)
 #endif  // __HIP_DEVICE_COMPILE__
 }
@@ -523,6 +574,10 @@ k_gemm_dma(const GemmArgs g) { gemm_dma_body<T, NREP, WGM, NSTAGE, LNF, false>(g
 template <typename T, int NREP>
 __global__ void __launch_bounds__(512, 2)
 k_gemm_h8(const GemmArgs g) { gemm_dma_body<T, NREP, 4, 2, 0, true>(g); }
+
+template <typename T, int NREP>
+__global__ void __launch_bounds__(512, 2)
+k_gemm_up4(const GemmArgs g) { gemm_dma_body<T, NREP, 4, 2, 0, false, true>(g); }
 
 
 // ---- split-K (small M, long K: the 8x8 / 16x16-level convs of a one-prompt batch have 8-20 tiles for 256 CUs and a
@@ -627,6 +682,18 @@ int dispatch_dma(int nrep, const GemmArgs& g, hipStream_t st) {
     case 2: return launch_dma<T, 2, 2>(g, st);
     default: return launch_dma<T, 1, 2>(g, st);
   }
+}
+
+// the phase form of an upsampler conv (UP4): pinned to the 256-row tiles (family 5 of the launch record), whatever the grid --
+// the op's tile must not depend on the batch, and a sample's rows are whole tiles
+template <typename T>
+int dispatch_up4(int nrep, const GemmArgs& g, hipStream_t st) {
+  const int grid = g.tiles_m * g.tiles_n;
+  record_gemm_launch(5, T::kDtype, nrep, 4, 2, 0, g.tiles_m, g.tiles_n, 1, 0);
+  if (nrep == 10) hipLaunchKernelGGL((k_gemm_up4<T, 10>), dim3(grid), dim3(512), 0, st, g);
+  else if (nrep == 8) hipLaunchKernelGGL((k_gemm_up4<T, 8>), dim3(grid), dim3(512), 0, st, g);
+  else return SDN_E_INVALID;
+  return sdn_launch_status();
 }
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -745,6 +812,15 @@ static int sdn_gemm_impl(int dtype, const sdn_gemm_desc* d, const void* a, const
   const bool res_pre = d->res_pre && residual && !x3 && !rowgate && !d->residual_bcast && d->split_k <= 1 && !partials && !ln_c &&
                        d->out_kind == SDN_OUT_BF16 && n_valid == d->N && d->act == SDN_ACT_NONE;
   int nrep = sdn_gemm_pick_tile(d->M, d->N, d->K, d->act, ((residual && !x3 && !res_pre) || rowgate) ? 1 : 0);
+  // phase form of an upsampler conv: bias, column statistics and a whole-width 16-bit output, nothing else; its own pinned tile
+  const bool up4 = d->a_mode == SDN_A_CONV3X3 && d->upsample == 2;
+  if (up4) {
+    if (x3 || rowbias || rowgate || residual || d->act != SDN_ACT_NONE || n_valid != d->N || d->out_kind != SDN_OUT_BF16 || d->split_k > 1 ||
+        partials || ln_c || ln_d || d->stride != 1 || d->asym_pad || d->K != 4 * d->Cin || d->Hs <= 0 || d->Ws <= 0)
+      return SDN_E_INVALID;
+    nrep = sdn_conv_up4_tile(d->Hs, d->Ws, d->Cin, d->N);
+    if (nrep == 0 || (long)4 * d->N * d->K * 2 >= (1L << 31)) return SDN_E_INVALID;
+  }
   if ((ln_c || ln_d) && nrep == 8 && d->N % 320 == 0) nrep = 10;          // (the LayerNorm-folded forms have no 256-wide instantiation)
   if (h8) {                                                                // the fp8 k-tiles exist on the 256-row tiles only; the 256-wide
     if (d->N % 256 == 0) nrep = 8;                                         // one holds its fp8 body in registers (the 320-wide one spills
@@ -763,7 +839,7 @@ static int sdn_gemm_impl(int dtype, const sdn_gemm_desc* d, const void* a, const
     g.K1 = (d->K1 > 0 && d->K1 < d->K) ? d->K1 : d->K;
     if (g.K1 != d->K && (!a2 || (g.K1 % BK) != 0)) return SDN_E_INVALID;
   } else if (d->a_mode == SDN_A_CONV3X3) {
-    if (d->Cin <= 0 || (d->Cin % BK) != 0 || d->K != 9 * d->Cin || d->Hs <= 0 || d->Ws <= 0 || d->Ho <= 0 ||
+    if (d->Cin <= 0 || (d->Cin % BK) != 0 || d->K != (up4 ? 4 : 9) * d->Cin || d->upsample < 0 || d->upsample > 2 || d->Hs <= 0 || d->Ws <= 0 || d->Ho <= 0 ||
         d->Wo <= 0 || (d->stride != 1 && d->stride != 2) || d->M % (d->Ho * d->Wo) != 0)
       return SDN_E_INVALID;
     const int Hi = d->upsample ? 2 * d->Hs : d->Hs, Wi = d->upsample ? 2 * d->Ws : d->Ws;
@@ -853,6 +929,10 @@ static int sdn_gemm_impl(int dtype, const sdn_gemm_desc* d, const void* a, const
                          (const unsigned short*)residual, d->residual_bcast, g.ldc, d->act, (unsigned short*)out);
     return sdn_launch_status();
   }
+  if (up4) {
+    ++g_gemm_launches[1];
+    return dtype == 0 ? dispatch_up4<SdnBF16>(nrep, g, st) : dispatch_up4<SdnF16>(nrep, g, st);
+  }
   if (nrep == 10 && g_gemm_variant != 13) {                    // variant 13: slab convolution off (A/B, equality tests)
     const int rc = dispatch_conv_slab(dtype, g, st);
     if (rc != SDN_GEMM_NOT_SLAB) { ++g_gemm_launches[0]; return rc; }
@@ -937,6 +1017,54 @@ extern "C" int sdn_ln_fold(int32_t dtype, const void* w, const float* gamma, con
   else
     hipLaunchKernelGGL((k_ln_fold<SdnBF16>), dim3(rows), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)w, gamma, beta,
                        bias, cols, (unsigned short*)w_folded, c, dvec);
+  return sdn_launch_status();
+}
+
+// ---- phase weights of an upsampler conv (sdn_conv_up4_weights): prepare-time, one thread per output element ---------------
+// Row (y + a - 1 + py) of the stored map is what taps ty of the nine-tap conv over the upsampled map read when
+//   py = 0: a = 0 <- ty {0},    a = 1 <- ty {1, 2};      py = 1: a = 0 <- ty {0, 1},    a = 1 <- ty {2}
+// and the same in x.  out[p][n][(2a + b) Cin + c] = the fp32 sum of those 1, 2 or 4 stored taps, ty-major, tx-minor, rounded once.
+int sdn_conv_up4_tile(int Hs, int Ws, int Cin, int N) {
+  if (Hs <= 0 || Ws < 8 || Cin <= 0 || N <= 0 || ((long)Hs * Ws) % 256 != 0 || Cin % BK != 0) return 0;
+  return N % 320 == 0 ? 10 : (N % 256 == 0 ? 8 : 0);
+}
+
+namespace {
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_conv_up4_weights(const unsigned short* __restrict__ w9, int N, int Cin, unsigned short* __restrict__ out) {
+  const long per = (long)N * 4 * Cin;
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= 4 * per) return;
+  const int p = (int)(e / per);
+  const long r = e - p * per;
+  const int n = (int)(r / (4 * Cin)), k = (int)(r - (long)n * 4 * Cin);
+  const int tap = k / Cin, c = k - tap * Cin;
+  const int py = p >> 1, px = p & 1, a = tap >> 1, b = tap & 1;
+  const int ty0 = a == 0 ? 0 : (py ? 2 : 1), ty1 = a == 0 ? (py ? 1 : 0) : 2;
+  const int tx0 = b == 0 ? 0 : (px ? 2 : 1), tx1 = b == 0 ? (px ? 1 : 0) : 2;
+  float acc = 0.f;
+  bool first = true;
+  for (int ty = ty0; ty <= ty1; ++ty)
+    for (int tx = tx0; tx <= tx1; ++tx) {
+      const float v = T::to_f(w9[(long)n * 9 * Cin + (3 * ty + tx) * Cin + c]);
+      acc = first ? v : acc + v;
+      first = false;
+    }
+  out[e] = (unsigned short)(T::pack2(acc, 0.f) & 0xffffu);
+}
+}  // namespace
+
+extern "C" int sdn_conv_up4_weights(int32_t dtype, const void* w9, int32_t N, int32_t Cin, void* out, void* stream) {
+  if (!w9 || !out || N <= 0 || Cin <= 0 || dtype < 0 || dtype > 1) return SDN_E_INVALID;
+  const long total = (long)16 * N * Cin;
+  const unsigned grid = (unsigned)((total + 255) / 256);
+  if (dtype == 1)
+    hipLaunchKernelGGL((k_conv_up4_weights<SdnF16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)w9, N, Cin,
+                       (unsigned short*)out);
+  else
+    hipLaunchKernelGGL((k_conv_up4_weights<SdnBF16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)w9, N, Cin,
+                       (unsigned short*)out);
   return sdn_launch_status();
 }
 

@@ -112,7 +112,7 @@ int dispatch_conv_slab(int dtype, const GemmArgs& g, hipStream_t st);
 
 // Launch record (host side, diagnostics only: sdn_debug_gemm_last_launch): what the last GEMM-family launch ran.  Set where
 // the template parameters are known; it changes no launch.  family: 1 = k_gemm_dma, 2 = k_conv_slab, 3 = split-K slices of
-// k_gemm_dma + k_splitk_reduce, 4 = k_ffn320.  aux = k_conv_slab's map width W (0 elsewhere).
+// k_gemm_dma + k_splitk_reduce, 4 = k_ffn320, 5 = k_gemm_up4 (upsampler conv in phase form).  aux = k_conv_slab's map width W (0 elsewhere).
 enum { SDN_LL_FAMILY, SDN_LL_DTYPE, SDN_LL_NREP, SDN_LL_WGM, SDN_LL_NSTAGE, SDN_LL_LNF, SDN_LL_TILES_M, SDN_LL_TILES_N,
        SDN_LL_SPLITS, SDN_LL_AUX, SDN_LL_COUNT };
 void record_gemm_launch(int family, int dtype, int nrep, int wgm, int nstage, int lnf, int tiles_m, int tiles_n, int splits, int aux);

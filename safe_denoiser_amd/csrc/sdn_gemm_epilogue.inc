@@ -299,8 +299,15 @@
     for (int e = tid; e < ROWS_PER_PASS * cpr; e += THREADS) {
       const int r = e / cpr, c = e - r * cpr;
       const int m = m0 + pass * ROWS_PER_PASS + r;
+#ifdef SDN_EPI_OUT_ROW                                        // (k_gemm_up4: GEMM row -> row of the upsampled map)
+      // ONLY this staged store remaps rows: the direct stores above (f32 / NCHW / ragged / x3 outputs) index by GEMM row, so the
+      // phase mode must never reach them -- sdn_gemm_impl admits it with a whole-width 16-bit output only; relax that check and these paths need the remap too
+      if (m < g.M && !(g.dbg & 1))
+        *reinterpret_cast<u32x4*>(out16 + (long)SDN_EPI_OUT_ROW(m) * g.ldc + col0 + c * 8) = *reinterpret_cast<const u32x4*>(smem + r * CW + c * 16);
+#else
       if (m < g.M && !(g.dbg & 1))
         *reinterpret_cast<u32x4*>(out16 + (long)m * g.ldc + col0 + c * 8) = *reinterpret_cast<const u32x4*>(smem + r * CW + c * 16);
+#endif
     }
     // (after the stores have been issued: they drain while the sums are taken)
     if (g.col_stats) {                                       // column sums of this pass's staged slab (16-bit values, as stored)

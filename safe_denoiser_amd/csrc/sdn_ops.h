@@ -28,6 +28,11 @@ int sdn_linear_pair_fold(int dtype, const void* wa, const void* wb, const float*
 // (square side x side map, M = batch * side^2 output rows, N padded output channels).
 int sdn_conv_slab_shape_ok(int M, int N, int Cin, int side, int stride, int upsample, int asym_pad, int out_kind, int n_valid);
 
+// Upsampler convs (3x3 over a nearest-2x upsampled Hs x Ws map) that take the phase form (sdn_gemm_desc.upsample = 2): the
+// 256-row tile that serves N (10 or 8), or 0 when the shape does not qualify -- Hs Ws a multiple of 256 (whole tiles per sample
+// and phase), Ws >= 8, Cin a multiple of 64.  Depends on the architecture only, never on the batch.
+int sdn_conv_up4_tile(int Hs, int Ws, int Cin, int N);
+
 // Launch record of the normalisation family (host side, diagnostics only: sdn_debug_norm_last_launch), set by the launchers of
 // sdn_norm.hip and sdn_f32.hip where the kernel is chosen.  kernel: 1 k_gn_stats + k_gn_finalize + k_gn_apply, 2 k_gn_finalize_cols
 // + k_gn_apply, 3 k_layernorm, 4 k_layernorm (adaLN), 5 k_row_stats, 6 k_gn_rows_stats + k_gn_rows_apply, 7 k_groupnorm_f32,

@@ -167,7 +167,7 @@ struct sdn_unet {
   bool ffn_own_stats = true;            // k_ffn320 takes norm3's row statistics from its own operand fragments (no sdn_row_stats pass)
   bool ffn_fuse = true;                 // ... and the GEGLU projection in front of them: one launch, hidden activation in LDS (C = 320)
                                         // contracted into ONE GEMM over [ff | h3] with the product weight (sdn_linear_pair_fold)
-  struct FoldJob { int64_t w, gamma, beta, bias, wf, c, d; int rows, cols; int kind = 0; int group = 0; };   // kind 0: LayerNorm fold; 1: linear pair; 2: bf16x3 weight expansion (sdn_expand3_weights)
+  struct FoldJob { int64_t w, gamma, beta, bias, wf, c, d; int rows, cols; int kind = 0; int group = 0; };   // kind 0: LayerNorm fold; 1: linear pair; 2: bf16x3 weight expansion (sdn_expand3_weights); 3: upsampler phase weights (sdn_conv_up4_weights: rows = N, cols = Cin)
   std::vector<FoldJob> fold_jobs;       // what sdn_unet_prepare has to compute into the SDN_P_DERIVED regions
   // Cross-attention K / V of the text (16 projections per forward, M = batch x 77) depend on the text operand alone, which the
   // denoising loop changes a handful of times in 50 steps: their outputs live in never-recycled workspace slots and the launches
@@ -182,6 +182,8 @@ struct sdn_unet {
   bool split_k = false;                 // sdn_unet_set_split_k: small-M GEMMs of the plan take the split-K form (off by
                                         // default: it changes fp32 summation order with the batch size, and batch rows are
                                         // otherwise bit-identical whatever the batch)
+  bool conv_up4 = true;                 // sdn_unet_set_conv_up4: qualifying upsampler convs of the 16-bit UNet plans in phase form (K = 4 Cin);
+                                        // the choice is a function of the architecture alone -- never of the batch
   struct GraphKey {
     int batch; const void *w, *lat, *text, *pooled, *out, *ws;
     bool operator<(const GraphKey& o) const {
@@ -239,6 +241,11 @@ struct Builder {
   bool plan_bad = false;          // an emitter met an inconsistency: the finished plan gets ws_bytes = -1
   bool force_x3t_next = false;    // the next gemm() takes the operand-expansion form although its A operand is not a workspace tensor (text states)
   std::set<int64_t> pairs;        // workspace offsets that hold pair rows
+  // upsampler convs that qualify for the phase form: their derived weight regions are registered by finish_up4() AFTER every real
+  // parameter (no existing manifest offset moves), which then fills in the `w` of the ops emitted in that form (op >= 0)
+  struct Up4 { int64_t op; int64_t w9; int N, Cin; };
+  std::vector<Up4> up4_pending;
+  void finish_up4();
   struct Res { std::string pfx; int cout; };
 
   // ---- parameters, activations, bf16x3 helpers and shared op emitters (sdn_plan_core.hip) -----------

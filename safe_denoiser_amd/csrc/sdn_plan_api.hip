@@ -160,6 +160,11 @@ int sdn_unet_prepare(sdn_unet* u, void* weights, void* stream) {
       if (rc2 != SDN_OK) return rc2;
       continue;
     }
+    if (j.kind == 3) {
+      const int rc3 = sdn_conv_up4_weights(dt, W + j.w, j.rows, j.cols, W + j.wf, stream);
+      if (rc3 != SDN_OK) return rc3;
+      continue;
+    }
     if (j.kind == 1) {
       const int rc1 = sdn_linear_pair_fold(dt, W + j.w, W + j.gamma, (const float*)(W + j.beta), (const float*)(W + j.bias), j.rows, j.cols,
                                            W + j.wf, (float*)(W + j.c), stream);
@@ -325,6 +330,11 @@ void sdn_unet_set_split_k(sdn_unet* u, int32_t on) {
                                                                                        // erf-GELU is a lean epilogue only: no split-K form)
   if (u->dtype() >= 2) return;                                 // fp32-storage modes have no split-K form
   set_plan_toggle(u, &sdn_unet::split_k, on != 0);             // plans are rebuilt with / without partial buffers
+}
+
+void sdn_unet_set_conv_up4(sdn_unet* u, int32_t on) {
+  if (!u || u->kind != UNET || u->dtype() >= 2 || u->conv_up4 == (on != 0)) return;   // (only the 16-bit UNet plans have the form)
+  set_plan_toggle(u, &sdn_unet::conv_up4, on != 0);            // the derived regions stay registered: the manifest does not change
 }
 
 void sdn_unet_set_graph_mode(sdn_unet* u, int32_t on) {

@@ -149,7 +149,8 @@ void Builder::gemm(int64_t M, int N, int K, Ref a, Ref w, Ref bias, Ref out, int
 void Builder::push_gemm(Op& o) {
   o.col = pending_cols; pending_cols = Ref();
   const int nv = o.gd.n_valid > 0 ? o.gd.n_valid : o.gd.N;
-  const int split = (!u->split_k || nv != o.gd.N) ? 1 : sdn_gemm_pick_split(o.gd.M, o.gd.N, o.gd.K, o.gd.act, o.gd.out_kind);
+  const int split = (!u->split_k || nv != o.gd.N || (o.gd.a_mode == SDN_A_CONV3X3 && o.gd.upsample == 2)) ? 1
+                    : sdn_gemm_pick_split(o.gd.M, o.gd.N, o.gd.K, o.gd.act, o.gd.out_kind);
   if (split > 1) {
     const int64_t bytes = (int64_t)split * o.gd.M * o.gd.N * 4;
     const int64_t off = arena.alloc(bytes);
@@ -200,12 +201,39 @@ void Builder::conv3x3(const Act& in, int cout, int n_pad, Ref w, Ref bias, Ref o
   o.flops = 2.0 * (double)o.gd.M * (double)cout * (double)o.gd.K;
   o.bytes = 2.0 * ((double)B * in.side * in.side * in.C + (double)n_pad * o.gd.K + (double)o.gd.M * cout) +
             (residual.space != SP_NONE ? 2.0 * (double)o.gd.M * cout : 0.0);      // + the residual map the epilogue adds
+  // Upsampler of a 16-bit UNet plan whose shape qualifies (architecture only, never the batch): the phase form -- four 2x2 convs
+  // over the stored map, K = 4 Cin, weights = the derived region finish_up4() registers.  o.flops stays the nine-tap (algorithmic)
+  // count, so the per-launch TFLOP/s of these rows is above what the matrix pipe executed.  Never split-K (push_gemm).
+  const int up4 = (upsample == 1 && u->kind == UNET && es == 2 && stride == 1 && !asym_pad && out_kind == SDN_OUT_BF16 && n_valid == 0 &&
+                   n_pad == cout && residual.space == SP_NONE && rowbias.space == SP_NONE && w.space == SP_W)
+                      ? sdn_conv_up4_tile(in.side, in.side, in.C, n_pad) : 0;
+  if (up4) {
+    up4_pending.push_back({u->conv_up4 ? (int64_t)plan->ops.size() : -1, w.off, n_pad, in.C});
+    if (u->conv_up4) {
+      o.gd.K = 4 * in.C; o.gd.upsample = 2; o.gd.res_pre = 0;
+      o.bytes = 2.0 * ((double)B * in.side * in.side * in.C + 4.0 * n_pad * o.gd.K + (double)o.gd.M * cout);
+      snprintf(o.label, sizeof(o.label), "k_conv_up4<%d>", up4);
+      push_gemm(o);
+      return;
+    }
+  }
   if (Ho == in.side && sdn_conv_slab_shape_ok(o.gd.M, n_pad, in.C, in.side, stride, upsample, asym_pad, out_kind, n_valid) &&
       sdn_gemm_pick_tile(o.gd.M, n_pad, o.gd.K, SDN_ACT_NONE) == 10)
     snprintf(o.label, sizeof(o.label), "k_conv_slab<%d>", in.side);
   else
     snprintf(o.label, sizeof(o.label), "k_gemm<%d>", sdn_gemm_pick_tile(o.gd.M, n_pad, o.gd.K, SDN_ACT_NONE));
   push_gemm(o);
+}
+// End of a build: the phase-weight regions of the qualifying upsamplers go behind every real parameter, in plan order.
+void Builder::finish_up4() {
+  for (const Up4& p : up4_pending) {
+    const std::string name = "up4@" + std::to_string((long long)p.w9);
+    const bool fresh = u->param_index.find(name) == u->param_index.end();
+    Ref d = derived(name, (int64_t)16 * p.N * p.Cin * 2);
+    if (fresh) { sdn_unet::FoldJob j{p.w9, -1, -1, -1, d.off, -1, -1, p.N, p.Cin}; j.kind = 3; u->fold_jobs.push_back(j); }
+    if (p.op >= 0) plan->ops[(size_t)p.op].w = d;
+  }
+  up4_pending.clear();
 }
 void Builder::groupnorm(const Act& x, const Act* x2, float eps, int silu, Ref gamma, Ref beta, const Act& out) {
   Op o; o.kind = OP_GN; o.a = R(x); if (x2) o.a2 = R(*x2);

@@ -444,6 +444,7 @@ void Builder::build() {
   drop(cur);
   conv3x3(g, c.out_channels, npad, cow, cob, Ref{SP_OUT, 0}, 1, 0, Ref(), Ref(), 0, SDN_OUT_F32_NCHW, c.out_channels);
   drop(g);
+  finish_up4();
   plan->kv_base = Arena::up(arena.peak);
   plan->ws_bytes = plan_bad ? -1 : plan->kv_base + kv_top;
 }

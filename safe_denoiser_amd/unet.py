@@ -70,6 +70,7 @@ class UNet2DConditionModel(EngineModel):
                             norm_groups=cfg["norm_num_groups"],
                             dtype=code, latent_repeat=self.latent_repeat)
         self.tail_split = False            # set_tail_split(): see _tail_split_of
+        self.conv_up4 = True               # set_conv_up4(): mirrors the handle's switch (on by default)
         self._create("sdn_unet_create", c)
 
     # ---- parameters ---------------------------------------------------------------------------------
@@ -93,6 +94,8 @@ class UNet2DConditionModel(EngineModel):
         net = UNet2DConditionModel(text_len=self.text_len, dtype=self.dtype, precision=self.precision,
                                    latent_repeat=self.latent_repeat if latent_repeat is None else latent_repeat, **vars(self.config))
         net._weights = self._weights
+        if not self.conv_up4:
+            net.set_conv_up4(False)
         return net
 
     # ---- forward --------------------------------------------------------------------------------------
@@ -113,6 +116,15 @@ class UNet2DConditionModel(EngineModel):
         """Small-batch option (sdn_unet_set_split_k): under-filled GEMMs run in split-K form.  Rebuilds the plans, so the
         cached workspaces are dropped.  Off by default (keeps outputs bit-identical across batch sizes)."""
         _lib.lib().sdn_unet_set_split_k(self._h, 1 if on else 0)
+        self._ws = {}
+        return self
+
+    def set_conv_up4(self, on: bool = True):
+        """Upsampler convs in phase form (sdn_unet_set_conv_up4; on by default): four 2x2 convs over the stored map with summed
+        tap weights instead of nine taps over the upsampled one.  Off = the nine-tap op (A/B, tests).  Rebuilds the plans; the
+        manifest and the packed weights do not change."""
+        _lib.lib().sdn_unet_set_conv_up4(self._h, 1 if on else 0)
+        self.conv_up4 = bool(on)
         self._ws = {}
         return self
 

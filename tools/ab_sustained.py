@@ -27,6 +27,8 @@ for rnd in range(3):
         elif os.environ.get("LNPRE") == "1":                     # second arm = every folded LayerNorm's row statistics from the pre-pass (LNF = 2 kernels)
             import ctypes as C
             sda.lib().sdn_debug_set_ln_prepass_all(C.c_void_p(u._h.value), 1 if v else 0)
+        elif os.environ.get("UP4") == "1":                       # second arm = upsampler convs as the nine-tap op (sdn_unet_set_conv_up4 off)
+            u.set_conv_up4(not v)
         elif TEXTVER:
             u.set_text_version(5 if v else 0)
         else:

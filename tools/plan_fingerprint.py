@@ -31,7 +31,7 @@ UNET_TOGGLES = [("plain", None, 0), ("split_k", "sdn_unet_set_split_k", 1), ("x3
                 ("ln_prepass_all=1", "sdn_debug_set_ln_prepass_all", 1), ("ffn_fuse=0", "sdn_debug_set_ffn_fuse", 0),
                 ("ff_fuse=0", "sdn_debug_set_ff_fuse", 0), ("ffn_own_stats=0", "sdn_debug_set_ffn_own_stats", 0),
                 ("x3_pairs=0", "sdn_debug_set_x3_pairs", 0), ("gn_fuse=0", "sdn_debug_set_gn_fuse", 0),
-                ("subbatch=24MiB", "sdn_debug_set_subbatch_bytes", 24 << 20)]
+                ("subbatch=24MiB", "sdn_debug_set_subbatch_bytes", 24 << 20), ("conv_up4=0", "sdn_unet_set_conv_up4", 0)]
 i4 = C.c_int32 * 4
 
 
