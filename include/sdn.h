@@ -189,7 +189,9 @@ int sdn_flow_renoise(const float* x0r, const float* x1, const float* z, int64_t 
 #define SDN_ACT_GELU      7   /* x * Phi(x), the exact (erf) GELU, not gated -- OpenCLIP bigG's MLP (hidden_act = "gelu").  16-bit GEMMs: a
                                staged 16-bit output with no residual / row gate / split-K only (their epilogue evaluates the
                                erf form the SDN_ACT_GEGLU gate uses, |error| <= 2.6e-5); sdn_gemm_f32 / sdn_gemm_x3: erff, any
-                               output.  Code 6 is not assigned: every GEMM entry point rejects it                          */
+                               output.  Codes 6 and 8 are not assigned: every GEMM entry point rejects them                */
+#define SDN_ACT_RELU      9   /* max(x, 0) (a NaN stays a NaN) -- BasicConv2d of the Inception-v3 tower.  sdn_gemm_f32 / sdn_gemm_x3 only:
+                               the 16-bit GEMM entry points reject it                                                       */
 #define SDN_OUT_BF16      0   /* [M, ldc] bf16                                                */
 #define SDN_OUT_F32       1   /* [M, ldc] f32                                                 */
 #define SDN_OUT_F32_NCHW  2   /* [B, n_valid, rows_per_batch] f32 (conv_out -> latent layout) */
@@ -873,6 +875,63 @@ void sdn_unet_set_split_k(sdn_unet* u, int32_t on);
  * entries, 16 N Cin elements per qualifying upsampler: 66 MB for SD-v1.4, part of sdn_unet_weight_bytes and filled by
  * sdn_unet_prepare even when the switch is off, so that the packed buffer never depends on it); changing the switch rebuilds the plans.  No effect on fp32-storage plans and on handles that are not a UNet. */
 void sdn_unet_set_conv_up4(sdn_unet* u, int32_t on);
+
+/* ---- Inception-v3 pool3 tower: the feature extractor of FID and KID ---------------------------------------------------------
+ * Replaces `InceptionV3([3])(batch)[0]` of pytorch-fid as the reference vendors it (evaluations/utils/inception.py:16-163, built by
+ * evaluations/utils/fid.py:203-215): torchvision's Inception3 trunk (third party) with the FID patches -- pad-excluding average
+ * pools in Mixed_5b..5d, 6b..6e and 7b, a max pool in Mixed_7c -- up to the global average pool: pixels [B, 3, H, W] in [0, 1] ->
+ * features [B, 2048] f32.  fp32 storage only: every one of the 94 convolutions is "patch rows, then sdn_gemm_f32" with
+ * bias + SDN_ACT_RELU in the epilogue, each branch written straight into its channel slice of the block's concatenation (ldc);
+ * a 1x1 stride-1 convolution over a map whose channel count is a multiple of 64 reads the map itself.
+ * Handle = sdn_unet (manifest / weights / workspace / flops through the sdn_unet_* queries).  Manifest keys are pytorch-fid's
+ * state_dict keys: per BasicConv2d `<name>.conv.weight` and `<name>.bn.{weight,bias,running_mean,running_var}`.  BatchNorm
+ * (eps 1e-3) is FOLDED by the loader, in float64 and rounded once: the `conv.weight` region holds
+ * w[o, c, ky, kx] * gamma[o] / sqrt(var[o] + eps) as f32 [n_padded][kpad] in (ky, kx, c) column order (kpad = kh kw cin rounded up
+ * to 64, n_padded = cout rounded up to 32, zero filled), the `bn.bias` region beta[o] - mean[o] * gamma[o] / sqrt(var[o] + eps)
+ * as f32 [n_padded]; the other three bn regions are kept as given and not read by any kernel. */
+typedef struct sdn_inception_config {
+  int32_t image_size;                    /* side of the square map the trunk runs on: 299 for FID; 75 .. 1024              */
+  int32_t normalize_input;               /* 1 = the trunk sees 2 x - 1 (pytorch-fid's normalize_input), 0 = x              */
+  int32_t dtype;                         /* 2 (fp32 storage on the f32-input matrix cores); everything else is refused     */
+} sdn_inception_config;
+typedef struct sdn_inception_conv {      /* one BasicConv2d of the trunk, in manifest (= execution) order                   */
+  char    name[64];                      /* e.g. "Mixed_6b.branch7x7dbl_2"                                                 */
+  int32_t cin, cout, kh, kw, stride, pad_h, pad_w;
+  int32_t kpad, n_padded;                /* the packed weight is f32 [n_padded][kpad]                                      */
+} sdn_inception_conv;
+int sdn_inception_create(const sdn_inception_config* cfg_host, sdn_unet** out_host);
+int sdn_inception_conv_count(const sdn_unet* inception);
+int sdn_inception_conv_info(const sdn_unet* inception, int32_t index, sdn_inception_conv* info_host);
+/* features [B, 2048] f32 = trunk(pixels f32 [B, 3, h, w] NCHW).  resize = 1: the pixels are first resized to image_size x image_size
+ * (sdn_resize_bilinear_f32; any h, w in 1 .. 8192); resize = 0: h == w == image_size.  A batch at which a patch matrix of the plan
+ * would reach 2 GiB is refused (SDN_E_INVALID; sdn_unet_workspace_bytes answers 0): 32 images fit at 299 x 299, whose largest patch
+ * matrix is 0.89 GB; callers chunk.  A sample's features do not depend on the batch it is in. */
+int sdn_inception_forward(sdn_unet* inception, const void* weights, const float* pixels, float* features, int32_t batch, int32_t h,
+                          int32_t w, int32_t resize, void* workspace, size_t workspace_bytes, void* stream);
+/* its building blocks; activations are NHWC f32, offsets 64-bit:
+ * sdn_patch_rows_f32: the patch matrix of one convolution.  in [B, h, w, c] -> out [B Ho Wo, kpad], Ho = (h + 2 pad_h - kh) /
+ *   stride_h + 1 (floor; Wo likewise), out[(b, oy, ox), (ky kw + kx) c + ci] = in[b, oy stride_h - pad_h + ky, ox stride_w - pad_w
+ *   + kx, ci]; taps in the padding and the columns kh kw c .. kpad are written as zeros.  kpad >= kh kw c, kpad % 64 == 0; in and
+ *   out 16-byte aligned; kh, kw <= 16, pad < kernel.
+ * sdn_pool3_f32: 3x3 pooling, stride 1 | 2, pad 0 | 1, floor output size.  mode SDN_POOL_MAX: the maximum over the taps inside the
+ *   map (nn.MaxPool2d(3, stride, pad)); SDN_POOL_AVG_NOPAD: their sum in (ky, kx) order over their COUNT
+ *   (F.avg_pool2d(x, 3, 1, 1, count_include_pad=False)).  out[(b, oy, ox), c0 + ci] with row stride ldo >= c0 + c: a channel slice
+ *   of a wider map; nothing outside the slice is written.
+ * sdn_resize_bilinear_f32: out NHWC [B, out_h, out_w, 3] = scale * F.interpolate(in NCHW [B, 3, h, w], (out_h, out_w),
+ *   mode="bilinear", align_corners=False) + shift -- no antialiasing (not Pillow's resample: that is sdn_image_resize_rect_u8).
+ *   The cell index and weight of an output index come from the exact fraction ((2 d + 1) in - out) / (2 out), clamped at 0; the
+ *   four taps are combined row by row in f32.  The same size in and out is a layout change (and scale, shift) only.
+ * sdn_spatial_mean_f32: out [B, c] = mean over p of in [B, hw, c] (AdaptiveAvgPool2d(1)): summed in p order in double, rounded
+ *   to f32 once. */
+#define SDN_POOL_MAX        0
+#define SDN_POOL_AVG_NOPAD  1
+int sdn_patch_rows_f32(const float* in, int32_t batch, int32_t h, int32_t w, int32_t c, int32_t kh, int32_t kw, int32_t stride_h,
+                       int32_t stride_w, int32_t pad_h, int32_t pad_w, int32_t kpad, float* out, void* stream);
+int sdn_pool3_f32(int32_t mode, const float* in, int32_t batch, int32_t h, int32_t w, int32_t c, int32_t stride, int32_t pad,
+                  float* out, int32_t ldo, int32_t c0, void* stream);
+int sdn_resize_bilinear_f32(const float* in_nchw, int32_t batch, int32_t h, int32_t w, int32_t out_h, int32_t out_w, float scale,
+                            float shift, float* out_nhwc, void* stream);
+int sdn_spatial_mean_f32(const float* in, int32_t batch, int32_t hw, int32_t c, float* out, void* stream);
 
 /* ---- opt-in measurement: HIP events around every launch of ONE forward, on the forward's own stream ---- */
 typedef struct sdn_profile_row {

@@ -78,6 +78,15 @@ class ClipVisionConfig(C.Structure):
                                          "projection_dim", "act", "dtype")]
 
 
+class InceptionConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("image_size", "normalize_input", "dtype")]
+
+
+class InceptionConv(C.Structure):
+    _fields_ = [("name", C.c_char * 64)] + [(n, C.c_int32) for n in ("cin", "cout", "kh", "kw", "stride", "pad_h", "pad_w", "kpad",
+                                                                     "n_padded")]
+
+
 class T5Config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("vocab_size", "d_model", "d_kv", "d_ff", "num_layers", "num_heads", "num_buckets",
                                          "max_distance")] + [("eps", C.c_float), ("dtype", C.c_int32)]
@@ -199,6 +208,14 @@ SIGNATURES = {
     "sdn_clip_normalize_u8": (C.c_int, [_vp, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp]),
     "sdn_image_resize_rect_u8": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _f32, _f32,
                                            _f32, _f32, _f32, _f32, _vp]),
+    "sdn_inception_create": (C.c_int, [C.POINTER(InceptionConfig), C.POINTER(_vp)]),
+    "sdn_inception_conv_count": (C.c_int, [_vp]),
+    "sdn_inception_conv_info": (C.c_int, [_vp, _i32, C.POINTER(InceptionConv)]),
+    "sdn_inception_forward": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "sdn_patch_rows_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "sdn_pool3_f32": (C.c_int, [_i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
+    "sdn_resize_bilinear_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp]),
+    "sdn_spatial_mean_f32": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "sdn_embed_row_scores": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp]),
     "sdn_t5_create": (C.c_int, [C.POINTER(T5Config), C.POINTER(_vp)]),
     "sdn_t5_workspace_bytes": (_sz, [_vp, _i32, _i32]),

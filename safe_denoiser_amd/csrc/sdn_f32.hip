@@ -109,6 +109,7 @@ __device__ __forceinline__ void gemm_row_epilogue(const GemmArgsF& g, const f32x
       else if (g.act == SDN_ACT_GELU_TANH) t = gelu_tanh_f(t);
       else if (g.act == SDN_ACT_QUICK_GELU) t = quick_gelu_f(t);
       else if (g.act == SDN_ACT_GELU) t = gelu_erf_f(t);
+      else if (g.act == SDN_ACT_RELU) t = t < 0.f ? 0.f : t;
       if (n + e >= g.n_valid) continue;
       if (g.out_kind == SDN_OUT_F32_NCHW) {
         const int p = m - b * g.rows_per_batch;
@@ -1081,7 +1082,7 @@ static int gemm_f32_storage(int x3, const sdn_gemm_desc* d, const void* a, const
   if (d->M < 0 || d->N <= 0 || d->K <= 0 || (d->K % 64) != 0 || (d->N % 32) != 0 || d->split_k > 1) return SDN_E_INVALID;
   if (d->M == 0) return SDN_OK;
   const int n_valid = d->n_valid > 0 ? d->n_valid : d->N;
-  if (n_valid > d->N || d->act < 0 || (d->act > 4 && d->act != SDN_ACT_GELU) || d->out_kind < 0 || d->out_kind > 2) return SDN_E_INVALID;
+  if (n_valid > d->N || d->act < 0 || (d->act > 4 && d->act != SDN_ACT_GELU && d->act != SDN_ACT_RELU) || d->out_kind < 0 || d->out_kind > 2) return SDN_E_INVALID;
   if (!al16(a) || !al16(w) || (a2 && !al16(a2)) || (bias && !al16(bias)) || (rowbias && !al16(rowbias)) ||
       (rowgate && !al16(rowgate)) || (reinterpret_cast<uintptr_t>(out) & 15))
     return SDN_E_INVALID;

@@ -16,7 +16,7 @@
 namespace sdn_plan {
 
 // which model a handle is: set once by its sdn_*_create, read by every entry point's guard and by get_plan
-enum ModelKind { UNET, MMDIT, VAE_DECODER, VAE_ENCODER, CLIP, CLIP_PROJ, T5, CLIP_VISION };
+enum ModelKind { UNET, MMDIT, VAE_DECODER, VAE_ENCODER, CLIP, CLIP_PROJ, T5, CLIP_VISION, INCEPTION };
 
 enum Space { SP_NONE = 0, SP_W = 1, SP_WS = 2, SP_IN = 3, SP_TEXT = 4, SP_OUT = 5, SP_POOLED = 6, SP_KV = 7, SP_OUT2 = 8 };
 // SP_IN / SP_OUT / SP_OUT2: a Call's primary input and its two outputs; SP_KV: the workspace's persistent tail (text K / V slots: written by one op, read by one op, never recycled)
@@ -32,6 +32,7 @@ struct Call {
   const int32_t* mask = nullptr;            // key-padding mask (nullable; CLIP and T5)
   int64_t out_bs = 0, out_rs = 0, out2_rs = 0;   // batch / row stride of out and row stride of out2 (elements), where the caller chooses them
   int64_t kv_base = 0;                      // not the caller's: run_plan's copy carries its plan's SP_KV base
+  int in_h = 0, in_w = 0;                   // Inception tower: height / width of the caller's pixels (the resize op's source)
   Call(const void* w, void* ws, size_t ws_bytes, int32_t b, void* s) : weights(w), workspace(ws), workspace_bytes(ws_bytes), batch(b), stream(s) {}
   const char* operator()(const Ref& r) const {
     switch (r.space) {
@@ -50,7 +51,8 @@ struct Call {
 
 enum OpKind { OP_TEMB, OP_CONV_IN, OP_GEMM, OP_GN, OP_LN, OP_ATTN, OP_PATCHIFY, OP_UNPATCHIFY, OP_LATENT_MIX, OP_SOFTMAX,
               OP_TRANSPOSE, OP_GAUSS, OP_REPEAT, OP_CLIP_EMBED, OP_MATTN, OP_ROWSTATS, OP_FFN, OP_SPLIT3,
-              OP_RMSNORM, OP_EMBED, OP_T5_BIAS, OP_BATTN, OP_EOS_ROWS, OP_COPY_ROWS, OP_PATCH_ROWS, OP_VISION_EMBED, OP_CLASS_ROWS };
+              OP_RMSNORM, OP_EMBED, OP_T5_BIAS, OP_BATTN, OP_EOS_ROWS, OP_COPY_ROWS, OP_PATCH_ROWS, OP_VISION_EMBED, OP_CLASS_ROWS,
+              OP_CONV_ROWS, OP_POOL3, OP_RESIZE, OP_SPATIAL_MEAN };
 
 struct Op {
   int kind;
@@ -73,6 +75,7 @@ struct Op {
   int heads = 0, nq = 0, nk = 0, hd = 0, ldq = 0, ldk = 0, ldv = 0, ldo = 0;
   float scale = 0.f;
   Ref k, v;
+  int kh = 0, kw = 0, sh = 0, sw = 0, ph = 0, pw = 0;   // OP_CONV_ROWS: kernel, stride, padding (input map batch x hw x hw x c1, kpad = c2); OP_POOL3: sh = stride, ph = pad
   char label[24] = {0};      // kernel symbol this op launches (profiling rows are aggregated by it)
   double flops = 0.0;        // algorithmic FLOPs of this launch
   double bytes = 0.0;        // algorithmic HBM bytes of this launch (operands read once + result written once)
@@ -149,6 +152,8 @@ struct sdn_unet {
   sdn_clip_proj_config pcfg;            // CLIP_PROJ: ccfg mirrors its encoder fields (same layers as CLIP)
   sdn_t5_config tcfg;
   sdn_clip_vision_config vis;           // CLIP_VISION
+  sdn_inception_config icfg;            // INCEPTION
+  std::vector<sdn_inception_conv> convs;   // INCEPTION: the trunk's convolutions in manifest order (sdn_inception_conv_info)
   std::vector<sdn_param_info> params;
   std::map<std::string, int> param_index;
   int64_t weight_bytes = 0;
@@ -209,6 +214,7 @@ struct sdn_unet {
       case sdn_plan::CLIP_PROJ: return pcfg.dtype;
       case sdn_plan::T5: return tcfg.dtype;
       case sdn_plan::CLIP_VISION: return vis.dtype;
+      case sdn_plan::INCEPTION: return icfg.dtype;
       default: return cfg.dtype;
     }
   }
@@ -304,6 +310,13 @@ struct Builder {
 
   // ---- CLIP ViT vision tower with projection (sdn_plan_vision.hip) -----------------------------------
   void build_clip_vision();
+
+  // ---- Inception-v3 pool3 tower (sdn_plan_inception.hip) ---------------------------------------------
+  void inception_conv(const std::string& name, const Act& in, int cout, int kh, int kw, int stride, int ph, int pw, const Act& out,
+                      int c0);
+  Act inception_conv_new(const std::string& name, const Act& in, int cout, int kh = 1, int kw = 1, int stride = 1, int ph = 0, int pw = 0);
+  void inception_pool(int mode, const Act& in, int stride, int pad, const Act& out, int c0);
+  void build_inception();
 };
 
 // n: the sequence length of a T5 plan (ignored by every other plan); 0 = the longest one (512), which bounds the workspace of any n

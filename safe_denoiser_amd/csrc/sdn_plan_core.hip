@@ -304,6 +304,7 @@ Plan* get_plan(sdn_unet* u, int batch, int n) {
     case CLIP: case CLIP_PROJ: b.build_clip(); break;
     case T5: b.build_t5(); break;
     case CLIP_VISION: b.build_clip_vision(); break;
+    case INCEPTION: b.build_inception(); break;
   }
   return &p;
 }

@@ -136,6 +136,18 @@ static int launch_op_f32(const sdn_unet* u, const Op& o, const Call& P, bool x3,
     case OP_COPY_ROWS:
       rc = sdn_copy_rows_strided(P(o.a), o.batch, o.hw, o.c1, 4, (void*)P(o.out), P.out_bs, P.out_rs, stream);
       break;
+    case OP_CONV_ROWS:
+      rc = sdn_patch_rows_f32((const float*)P(o.a), o.batch, o.hw, o.hw, o.c1, o.kh, o.kw, o.sh, o.sw, o.ph, o.pw, o.c2, (float*)P(o.out), stream);
+      break;
+    case OP_POOL3:
+      rc = sdn_pool3_f32(o.mod, (const float*)P(o.a), o.batch, o.hw, o.hw, o.c1, o.sh, o.ph, (float*)P(o.out), o.ldo, o.c2, stream);
+      break;
+    case OP_RESIZE:                              // source size: the call's; target: the plan's map (the same size = layout change only)
+      rc = sdn_resize_bilinear_f32((const float*)P(o.a), o.batch, P.in_h, P.in_w, o.hw, o.hw, o.scale, o.eps, (float*)P(o.out), stream);
+      break;
+    case OP_SPATIAL_MEAN:
+      rc = sdn_spatial_mean_f32((const float*)P(o.a), o.batch, o.hw, o.c1, (float*)P(o.out), stream);
+      break;
     case OP_MATTN:                               // 1.7 % of the encoder's FLOPs: exact f32 products in both fp32-storage modes
       rc = sdn_masked_attention_f32(P(o.a), P(o.k), P(o.v), (void*)P(o.out), P.mask, 1, o.batch, o.heads,
                                     o.nq, o.hd, o.ldq, o.ldk, o.ldv, o.ldo, o.scale, stream);
