@@ -599,14 +599,21 @@ typedef struct sdn_vae_config {
   int32_t block_out_channels[4];         /* 128, 256, 512, 512 (multiples of 64)                       */
   int32_t layers_per_block;              /* 2 (the decoder's up blocks run layers_per_block + 1 resnets) */
   int32_t norm_groups;                   /* 32                                                         */
-  int32_t dtype;                         /* 0 = bf16, 1 = fp16 activations / weights                   */
+  int32_t dtype;                         /* 0 = bf16, 1 = fp16 activations / weights; 2 = fp32 storage with exact f32 products on the
+                                          * f32-input matrix cores (sdn_gemm_f32); 3 = fp32 storage with bf16x3 contractions
+                                          * (sdn_gemm_x3 on f32 operands; no operand-expansion form).  The reference loads the VAE in
+                                          * fp32 with the rest of the pipeline (run_nudity.py:277).  Modes 2 / 3: the same manifest
+                                          * with f32 matrices, the plain operator chain (no GroupNorm statistics from conv epilogues,
+                                          * no phase-form upsamplers, no split-K), f32 probabilities and V^T in the mid-block
+                                          * attention; the entry points' fp32 NCHW tensors are the same in every mode */
 } sdn_vae_config;
 int sdn_vae_decoder_create(const sdn_vae_config* cfg_host, sdn_unet** out_host);
 /* image [B, out_channels, 8S.., 8S..] fp32 NCHW (the decoder's raw output, nominally in [-1, 1]) =
  * decoder(post_quant_conv(latent_scale * latents [B, latent_channels, S, S] fp32)).  latent_scale = 1 / scaling_factor
  * folds the first line of decode_latents.  Any batch: byte offsets inside one activation are 32-bit, so the entry
  * point replays the plan on chunks of at most 8 images (fewer at 1024 x 1024) against the same workspace, stream-ordered;
- * sdn_unet_workspace_bytes(vae, batch) returns the size of the largest chunk's workspace. */
+ * sdn_unet_workspace_bytes(vae, batch) returns the size of the largest chunk's workspace.  dtype 2 / 3: at most 4 images and
+ * every activation below 2^31 bytes (4 images at 512 x 512, 1 at 1024 x 1024; the derivation is at vae_chunk(), sdn_plan_api.hip). */
 int sdn_vae_decode(sdn_unet* vae, const void* weights, const float* latents, float latent_scale, float* image,
                    int32_t batch, void* workspace, size_t workspace_bytes, void* stream);
 /* Encoder half: the embed_fn of the proj_ref builder, `pipe.vae.encode(x).latent_dist.sample() * scaling_factor`
@@ -628,11 +635,17 @@ int sdn_image_postprocess(const float* image_nchw, int32_t batch, int32_t channe
  * out[b, co, p] = bias[co] + sum_ci w[co, ci] * in_scale * z[b, ci, p]   (1x1 conv on an fp32 NCHW map, C <= 16) */
 int sdn_latent_mix(const float* z, const float* w, const float* bias, int32_t batch, int32_t channels, int32_t hw,
                    float in_scale, float* out, void* stream);
-/* out[r, :] = softmax(scale * scores[r, :n]) as 16-bit (dtype 0 bf16 / 1 fp16); n % 4 == 0, n <= 16384 */
+/* out[r, :] = softmax(scale * scores[r, :n]) as 16-bit (dtype 0 bf16 / 1 fp16) or f32 (dtype 2); n % 4 == 0, n <= 16384, ld_* % 4
+ * == 0, scores 16-byte aligned, out 8-byte (dtype 2: 16-byte) aligned.  dtype 2 is the reference's fp32 softmax: t = scale * s
+ * rounded to f32, max and sum (a fixed pairwise tree) in f32, each probability expf(t - max) / sum with one correctly rounded
+ * division.  Anything else is SDN_E_INVALID. */
 int sdn_softmax_rows(int32_t dtype, const float* scores, int64_t ld_scores, int64_t rows, int32_t n, float scale,
                      void* out, int64_t ld_out, void* stream);
 /* out[c, r] = in[r, c] for a 16-bit [rows, cols] matrix */
 int sdn_transpose16(const void* in, int32_t rows, int32_t cols, int64_t ld_in, void* out, int64_t ld_out, void* stream);
+/* the same for 4-byte elements (V^T of the fp32-storage VAE plans): rows, cols > 0, ld_in >= cols, ld_out >= rows (elements), both
+ * pointers 4-byte aligned; SDN_E_INVALID otherwise */
+int sdn_transpose32(const void* in, int32_t rows, int32_t cols, int64_t ld_in, void* out, int64_t ld_out, void* stream);
 
 /* ---- CLIP text encoder ------------------------------------------------------------------------------
  * Replaces `self.text_encoder(input_ids, attention_mask=...)[0]` (transformers CLIPTextModel, third party), called at

@@ -190,6 +190,7 @@ SIGNATURES = {
     "sdn_latent_mix": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp]),
     "sdn_softmax_rows": (C.c_int, [_i32, _vp, _i64, _i64, _i32, _f32, _vp, _i64, _vp]),
     "sdn_transpose16": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _i64, _vp]),
+    "sdn_transpose32": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _i64, _vp]),
     "sdn_clip_create": (C.c_int, [C.POINTER(ClipConfig), C.POINTER(_vp)]),
     "sdn_clip_forward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
     "sdn_clip_embed": (C.c_int, [_i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),

@@ -298,6 +298,7 @@ struct Builder {
   // ---- AutoencoderKL decoder and encoder (sdn_plan_vae.hip) ------------------------------------------
   Act vae_resnet(const std::string& pfx, Act& x, int cout);
   Act vae_attention(const std::string& pfx, Act& x);
+  void vae_f32_rows();       // fp32-storage plans: the kernel labels and 4-byte operand traffic of the finished op list
   void build_vae();
   void build_vae_encoder();
 

@@ -1,6 +1,8 @@
 // Launch planner, C ABI: the sdn_*_create functions (the vision tower's is in sdn_plan_vision.hip) with their config validation, sdn_unet_prepare, the manifest / workspace /
 // FLOP queries, the forward and encode / decode entry points (each states the handle kinds it accepts), sdn_unet_set_* and the
 // undeclared debug hooks.
+#include <algorithm>
+
 #include "sdn_plan.h"
 
 using namespace sdn_plan;
@@ -64,7 +66,7 @@ int sdn_vae_decoder_create(const sdn_vae_config* cfg, sdn_unet** out) {
   if (!cfg || !out) return SDN_E_INVALID;
   if (cfg->n_levels < 1 || cfg->n_levels > 4 || cfg->layers_per_block < 1 || cfg->latent_channels <= 0 ||
       cfg->latent_channels > 16 || cfg->out_channels <= 0 || cfg->out_channels > 32 || cfg->sample_size <= 0 ||
-      cfg->norm_groups <= 0 || cfg->norm_groups > 64 || cfg->dtype < 0 || cfg->dtype > 1)
+      cfg->norm_groups <= 0 || cfg->norm_groups > 64 || cfg->dtype < 0 || cfg->dtype > 3)
     return SDN_E_INVALID;
   for (int i = 0; i < cfg->n_levels; ++i) {
     const int c = cfg->block_out_channels[i];
@@ -75,6 +77,10 @@ int sdn_vae_decoder_create(const sdn_vae_config* cfg, sdn_unet** out) {
   sdn_unet* u = new sdn_unet();
   memset(&u->cfg, 0, sizeof(u->cfg));
   u->cfg.norm_groups = cfg->norm_groups;
+  // fp32-storage modes: the plain operator chain.  gn_fuse off = no activation carries a statistics slot (act_gn), so want_stats
+  // selects nothing and every GroupNorm computes its own; the phase-form upsamplers are a 16-bit UNet form (Builder::conv3x3) and
+  // split-K stays off (sdn_unet_set_split_k refuses these modes)
+  if (cfg->dtype >= 2) { u->gn_fuse = false; u->ln_fold = false; u->ff_fuse = false; }
   u->vcfg = *cfg;
   u->kind = VAE_DECODER;
   get_plan(u, 1);
@@ -194,9 +200,37 @@ size_t sdn_unet_weight_bytes(const sdn_unet* u) { return u ? (size_t)u->weight_b
 // Images one plan invocation of a VAE takes: byte offsets inside one activation are 32-bit in the GEMM's DMA descriptors, so the
 // largest tensor (batch x side^2 x widest channel count x 2 B) must stay below 4 GiB; larger batches are cut into chunks INSIDE
 // the entry points (each chunk replays the same plan on the same workspace, stream-ordered).
+//
+// fp32-storage plans (dtype 2 / 3), what their kernels do with an offset (sdn_f32.hip, sdn_vae.hip):
+//   k_gemm_f32       A rows `(long)am * ld`, conv taps `(((long)pb * Hs + sy) * Ws + sx) * Cin`, weights `(long)wn * K`, outputs
+//                    `(long)m * ldc` and, NCHW, `((long)b * n_valid + n) * rows_per_batch + p`: 64-bit ELEMENT offsets on a float*;
+//   k_gemm_x3        both A-gather paths: plain `abase[i] * ld + kk` with `long abase, ld`; conv `abase[i] + ((long)sy * Ws + sx) *
+//                    Cin + c0` with `abase = (long)pb * Hs * Ws * Cin + 4 sc`; weights `long wbase`: 64-bit as well;
+//   k_gn_rows_*      `((long)b * hw) * c1 + c`, `(long)r * ld`, `row * C` with `long row`: 64-bit;
+//   k_conv_in_f32*   `long pix`, `(((long)b * cin + c) * H + iy) * W + ix`: 64-bit;
+//   k_latent_mix, k_softmax_rows_f32, k_transpose32: `long` products of a row index and a leading dimension.
+// What is 32-bit and signed in them are INDICES, not offsets: the output row `m` / `am` (< M = batch x side^2), the pixel index
+// within an image, `hw`, and the grid size.  batch x side^2 < 2^31 holds for thousands of images, so no kernel of these modes
+// forces a limit near the 16-bit plans'.  The limit is therefore chosen, from two things:
+//   * the workspace: the 16-bit plans stop at 8 images; at 4 bytes per element the same budget is 4;
+//   * a margin against an offset this reading missed: every activation of a chunk stays below 2^31 BYTES (the signed 32-bit
+//     range, not the unsigned one of the 16-bit rule), so even a byte offset held in an `int` would still be in range.
+// The largest activation is taken level by level, not as side^2 x the widest channel count (the 16-bit rule's over-estimate, kept
+// as it is for those plans): at the resolution of block_out_channels[j] a map has that many channels, or the next level's behind
+// the decoder's upsampler.  SD-v1.4 at 512 x 512: the 256-channel map behind up_blocks.2's upsampler, 268 MB per image; 8 images
+// are 2^31 bytes, 7 fit, and the workspace rule makes it 4.  1024 x 1024: 1 GiB per image, one image per chunk.
 static int vae_chunk(const sdn_unet* v) {
   const sdn_vae_config& c = v->vcfg;
   const int64_t side = (int64_t)c.sample_size << (c.n_levels - 1);
+  if (c.dtype >= 2) {
+    int64_t largest = 0;
+    for (int j = 0; j < c.n_levels; ++j) {
+      const int64_t s = side >> j, ch = std::max(c.block_out_channels[j], c.block_out_channels[j + 1 < c.n_levels ? j + 1 : j]);
+      largest = std::max(largest, s * s * ch * 4);
+    }
+    const int64_t cap = std::min<int64_t>(4, (((int64_t)1 << 31) - 1) / largest);
+    return cap < 1 ? 0 : (int)cap;
+  }
   int64_t cmax = 0;
   for (int i = 0; i < c.n_levels; ++i) if (c.block_out_channels[i] > cmax) cmax = c.block_out_channels[i];
   int64_t cap = (((int64_t)1 << 32) - 1) / (side * side * cmax * 2);

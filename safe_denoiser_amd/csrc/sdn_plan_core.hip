@@ -294,7 +294,7 @@ Plan* get_plan(sdn_unet* u, int batch, int n) {
   Builder b{u, &p};
   b.B = batch;
   b.seq = n;
-  b.es = u->dtype() >= 2 ? 4 : 2;                               // fp32 storage: SD-v1.4 UNet, CLIP and MMDiT plans
+  b.es = u->dtype() >= 2 ? 4 : 2;                               // fp32 storage: SD-v1.4 UNet, CLIP, MMDiT and VAE plans
   b.x3t = u->kind == UNET && u->dtype() == 3 && u->x3_expand;
   switch (u->kind) {
     case UNET: b.build(); break;

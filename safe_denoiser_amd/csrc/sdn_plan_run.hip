@@ -148,6 +148,16 @@ static int launch_op_f32(const sdn_unet* u, const Op& o, const Call& P, bool x3,
     case OP_SPATIAL_MEAN:
       rc = sdn_spatial_mean_f32((const float*)P(o.a), o.batch, o.hw, o.c1, (float*)P(o.out), stream);
       break;
+    case OP_LATENT_MIX:                          // VAE plans: fp32 NCHW on both sides in every storage mode
+      rc = sdn_latent_mix((const float*)P(o.a), (const float*)P(o.w), (const float*)P(o.bias), o.batch, o.c1, o.hw,
+                          o.mod ? o.scale : P.scalar /* decoder: the caller's latent_scale */, (float*)P(o.out), stream);
+      break;
+    case OP_SOFTMAX:                             // ... their d = C mid-block attention: f32 scores -> f32 probabilities
+      rc = sdn_softmax_rows(2, (const float*)P(o.a), o.c1, o.rows, o.c1, o.scale, (void*)P(o.out), o.c1, stream);
+      break;
+    case OP_TRANSPOSE:                           // ... and V^T as the "weight" operand of P V
+      rc = sdn_transpose32(P(o.a), (int)o.rows, o.c1, o.ldq, (void*)P(o.out), o.ldo, stream);
+      break;
     case OP_MATTN:                               // 1.7 % of the encoder's FLOPs: exact f32 products in both fp32-storage modes
       rc = sdn_masked_attention_f32(P(o.a), P(o.k), P(o.v), (void*)P(o.out), P.mask, 1, o.batch, o.heads,
                                     o.nq, o.hd, o.ldq, o.ldk, o.ldv, o.ldo, o.scale, stream);
@@ -301,7 +311,7 @@ static int launch_op_16(const sdn_unet* u, const Op& o, const Call& P, bool f16,
 // Launches every op of the plan on `stream`.  t_dev != nullptr: the timestep is read from device memory (graph mode).
 static int launch_ops(sdn_unet* u, const Plan* p, const Call& c, const float* t_dev, bool prof, void* stream, bool skip_text_kv = false) {
   const int sdt = u->dtype();
-  const bool f32 = sdt >= 2;                                                 // fp32-storage modes (SD-v1.4 UNet, CLIP and MMDiT plans)
+  const bool f32 = sdt >= 2;                                                 // fp32-storage modes (SD-v1.4 UNet, CLIP, MMDiT and VAE plans)
   for (size_t opi = 0; opi < p->ops.size(); ++opi) {
     const Op& o = p->ops[opi];
     if ((skip_text_kv && o.text_kv) || (o.kind == OP_COPY_ROWS && !c.out)) continue;   // K / V of an unchanged text stand; no last_hidden_state buffer was given

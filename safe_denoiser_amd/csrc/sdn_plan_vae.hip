@@ -68,15 +68,15 @@ Act Builder::vae_attention(const std::string& pfx, Act& x) {
   // 16384) -- reused block after block (stream order)
   const int qrows = hw > 4096 ? 4096 : hw;
   Act sc = act(qrows, hw, 0, 0, 4);
-  Act pr = act(qrows, hw);
+  Act pr = act(qrows, hw);                                         // probabilities and V^T in the storage type (f32 in the fp32-storage plans)
   Act vt = act(C, hw);
   const float scale = 1.0f / sqrtf((float)C);
   for (int b = 0; b < B; ++b) {
-    const int64_t img = (int64_t)b * hw * C * 2;
+    const int64_t img = (int64_t)b * hw * C * es;
     { Op o; o.kind = OP_TRANSPOSE; o.a = Ref{SP_WS, v.off + img}; o.out = R(vt); o.rows = hw; o.c1 = C; o.ldq = C;
       o.ldo = hw; o.bytes = 4.0 * hw * C; snprintf(o.label, sizeof(o.label), "k_transpose16"); plan->ops.push_back(o); }
     for (int r0 = 0; r0 < hw; r0 += qrows) {
-      const int64_t rowoff = (int64_t)r0 * C * 2;
+      const int64_t rowoff = (int64_t)r0 * C * es;
       { // S = Q K^T : A = this block's Q rows, "weight" operand = the image's K rows
         Op o; o.kind = OP_GEMM; memset(&o.gd, 0, sizeof(o.gd));
         o.gd.M = qrows; o.gd.N = hw; o.gd.K = C; o.gd.a_mode = SDN_A_PLAIN; o.gd.out_kind = SDN_OUT_F32;
@@ -103,6 +103,32 @@ Act Builder::vae_attention(const std::string& pfx, Act& x) {
   gemm(rows, C, C, R(at), ow, ob, R(out), SDN_ACT_NONE, R(x));
   drop(at);
   return out;
+}
+
+// fp32-storage plans (dtype 2 / 3): the shared emitters above label and size their ops for the 16-bit kernels.  The op list is the
+// same; what launch_op_f32 runs for each kind, and the algorithmic bytes at 4 B per element, are filled in here (FLOPs are
+// algorithmic and do not change with the storage type).
+void Builder::vae_f32_rows() {
+  const bool x3 = u->vcfg.dtype == 3;
+  for (Op& o : plan->ops) {
+    const char* label = nullptr;
+    switch (o.kind) {
+      case OP_GEMM: {
+        const sdn_gemm_desc& d = o.gd;
+        const double a_el = d.a_mode == SDN_A_CONV3X3 ? (double)(d.M / (d.Ho * d.Wo)) * d.Hs * d.Ws * d.Cin : (double)d.M * d.K;
+        const double out_el = (double)d.M * (d.n_valid > 0 ? d.n_valid : d.N);
+        o.bytes = 4.0 * (a_el + (double)d.N * d.K + out_el + (o.residual.space != SP_NONE ? out_el : 0.0));
+        label = (x3 && d.M >= 64) ? "k_gemm_x3" : "k_gemm_f32";            // (sdn_gemm_x3 hands fewer than 64 rows to the f32 tile)
+        break;
+      }
+      case OP_GN: o.bytes = 12.0 * (double)o.batch * o.hw * (o.c1 + o.c2); label = "k_gn_rows_f32"; break;   // two reads, one write
+      case OP_CONV_IN: o.bytes = 4.0 * (double)o.batch * o.hw * o.hw * (o.c1 + o.c2); label = "k_conv_in_f32"; break;
+      case OP_SOFTMAX: o.bytes = 8.0 * (double)o.rows * o.c1; label = "k_softmax_rows_f32"; break;
+      case OP_TRANSPOSE: o.bytes = 8.0 * (double)o.rows * o.c1; label = "k_transpose32"; break;
+      default: break;                                                       // k_latent_mix: fp32 NCHW on both sides in every mode
+    }
+    if (label) snprintf(o.label, sizeof(o.label), "%s", label);
+  }
 }
 
 void Builder::build_vae() {
@@ -152,6 +178,7 @@ void Builder::build_vae() {
   drop(cur);
   conv3x3(g, c.out_channels, npad, cow, cob, Ref{SP_OUT, 0}, 1, 0, Ref(), Ref(), 0, SDN_OUT_F32_NCHW, c.out_channels);
   drop(g);
+  if (es == 4) vae_f32_rows();
   plan->ws_bytes = arena.peak;
 }
 // AutoencoderKL encoder (the proj_ref builder's embed_fn, run_nudity.py:308): conv_in -> DownEncoderBlock2D x n
@@ -208,6 +235,7 @@ void Builder::build_vae_encoder() {
     o.flops = 2.0 * B * hw * (double)M2 * M2; o.bytes = 8.0 * B * hw * M2; snprintf(o.label, sizeof(o.label), "k_latent_mix");
     plan->ops.push_back(o); plan->flops += o.flops; }
   drop(mom);
+  if (es == 4) vae_f32_rows();
   plan->ws_bytes = arena.peak;
 }
 

@@ -5,7 +5,9 @@
 //   k_softmax_rows  softmax(scale * S) over fp32 rows -> 16-bit P (the decoder's single-head, d = 512 mid-block
 //                   attention is run as Q K^T GEMM -> row softmax -> P V GEMM: its head dim does not fit the flash
 //                   kernel's register tile, and it is 1.5 % of the decoder's FLOPs);
+//   k_softmax_rows_f32  the same with f32 probabilities (fp32-storage plans, sdn_vae_config.dtype 2 / 3);
 //   k_transpose16   [R, C] -> [C, R] 16-bit (V^T as the "weight" operand of the P V GEMM);
+//   k_transpose32   the same for 4-byte elements;
 //   k_image_post    (x / 2 + 0.5).clamp(0, 1) NCHW fp32 -> NHWC fp32 and / or round(255 x) uint8
 //                   (decode_latents + numpy_to_pil of the reference's pipelines, ...threshold_time.py:589-596).
 #include "sdn_common.h"
@@ -74,6 +76,76 @@ k_softmax_rows(const float* __restrict__ s, long ld_s, int n, float scale_log2e,
       pk.y = T::pack2(v[q].z * inv, v[q].w * inv);
       *reinterpret_cast<uint2*>(orow + 4 * i) = pk;
     }
+  }
+}
+
+// The same row softmax with f32 probabilities (fp32-storage VAE plans): the reference's arithmetic, t = scale * s rounded to f32,
+// p = expf(t - max t) / sum.  The sum is a fixed pairwise tree (the four lanes of a float4, a thread's NV groups, the wave butterfly,
+// the four waves): depth log2(n) <= 14 roundings for any row length, where a running sum would carry 64 per thread at n = 16384.
+// One correctly rounded division per probability (not a product with the rounded reciprocal).
+template <int NV>
+__global__ void __launch_bounds__(THREADS)
+k_softmax_rows_f32(const float* __restrict__ s, long ld_s, int n, float scale, float* __restrict__ out, long ld_o) {
+  __shared__ float red[2][THREADS / 64];
+  const float* row = s + (long)blockIdx.x * ld_s;
+  float* orow = out + (long)blockIdx.x * ld_o;
+  const int nv = n / 4;                                     // float4 groups
+  float4 v[NV];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int q = 0; q < NV; ++q) {
+    const int i = threadIdx.x + q * THREADS;
+    if (i < nv) {
+      v[q] = *reinterpret_cast<const float4*>(row + 4 * i);
+      v[q].x *= scale; v[q].y *= scale; v[q].z *= scale; v[q].w *= scale;
+      mx = fmaxf(fmaxf(fmaxf(mx, v[q].x), fmaxf(v[q].y, v[q].z)), v[q].w);
+    }
+  }
+  mx = wave_max(mx);
+  if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
+  float part[NV];
+#pragma unroll
+  for (int q = 0; q < NV; ++q) {
+    const int i = threadIdx.x + q * THREADS;
+    part[q] = 0.f;
+    if (i < nv) {
+      v[q].x = expf(v[q].x - mx); v[q].y = expf(v[q].y - mx); v[q].z = expf(v[q].z - mx); v[q].w = expf(v[q].w - mx);
+      part[q] = (v[q].x + v[q].y) + (v[q].z + v[q].w);
+    }
+  }
+#pragma unroll
+  for (int w = 1; w < NV; w *= 2)
+#pragma unroll
+    for (int q = 0; q + w < NV; q += 2 * w) part[q] += part[q + w];
+  const float ws = wave_sum(part[0]);
+  if ((threadIdx.x & 63) == 0) red[1][threadIdx.x >> 6] = ws;
+  __syncthreads();
+  const float sum = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+#pragma unroll
+  for (int q = 0; q < NV; ++q) {
+    const int i = threadIdx.x + q * THREADS;
+    if (i < nv) *reinterpret_cast<float4*>(orow + 4 * i) = make_float4(v[q].x / sum, v[q].y / sum, v[q].z / sum, v[q].w / sum);
+  }
+}
+
+// 4-byte elements, 64 x 64 tiles through LDS with rows of 65 dwords.  Both global sides are coalesced (a wave reads one 256-byte
+// row segment of `in` and writes one of `out`), and both LDS sides are free of bank conflicts: ds_write_b32 / ds_read_b32 bank a
+// dword address mod 32 within each 32-lane half; the row-wise writes of a wave touch 64 consecutive dwords, the column-wise reads
+// touch dword r * 65 + c for 32 consecutive r, i.e. banks (r + c) mod 32, all distinct (a 64-dword row would put them on ONE bank).
+__global__ void __launch_bounds__(THREADS)
+k_transpose32(const unsigned* __restrict__ in, int R, int C, long ld_in, unsigned* __restrict__ out, long ld_out) {
+  __shared__ unsigned tile[64][65];
+  const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
+  for (int e = threadIdx.x; e < 64 * 64; e += THREADS) {
+    const int r = e >> 6, c = e & 63;
+    tile[r][c] = (r0 + r < R && c0 + c < C) ? in[(long)(r0 + r) * ld_in + c0 + c] : 0u;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < 64 * 64; e += THREADS) {
+    const int c = e >> 6, r = e & 63;
+    if (r0 + r < R && c0 + c < C) out[(long)(c0 + c) * ld_out + r0 + r] = tile[r][c];
   }
 }
 
@@ -161,9 +233,18 @@ extern "C" int sdn_softmax_rows(int32_t dtype, const float* scores, int64_t ld_s
                                 void* out, int64_t ld_out, void* stream) {
   if (!scores || !out || rows < 0 || n <= 0 || (n & 3) || n > 64 * THREADS || ld_scores < n || ld_out < n ||
       (ld_scores & 3) || (ld_out & 3) || (reinterpret_cast<uintptr_t>(scores) & 15) ||
-      (reinterpret_cast<uintptr_t>(out) & 7) || dtype < 0 || dtype > 1 || rows > 0x7fffffffL)
+      (reinterpret_cast<uintptr_t>(out) & (dtype == 2 ? 15 : 7)) || dtype < 0 || dtype > 2 || rows > 0x7fffffffL)
     return SDN_E_INVALID;
   if (rows == 0) return SDN_OK;
+  if (dtype == 2) {                                           // f32 probabilities: the fp32-storage plans' softmax
+    if (n <= 16 * THREADS)
+      hipLaunchKernelGGL((k_softmax_rows_f32<4>), dim3((unsigned)rows), dim3(THREADS), 0, (hipStream_t)stream, scores, (long)ld_scores, n,
+                         scale, (float*)out, (long)ld_out);
+    else
+      hipLaunchKernelGGL((k_softmax_rows_f32<16>), dim3((unsigned)rows), dim3(THREADS), 0, (hipStream_t)stream, scores, (long)ld_scores, n,
+                         scale, (float*)out, (long)ld_out);
+    return sdn_launch_status();
+  }
   const float sl = scale * 1.4426950408889634f;
 #define SDN_SM_LAUNCH(TT, NV)                                                                                              \
   hipLaunchKernelGGL((k_softmax_rows<TT, NV>), dim3((unsigned)rows), dim3(THREADS), 0, (hipStream_t)stream, scores,           \
@@ -179,6 +260,16 @@ extern "C" int sdn_transpose16(const void* in, int32_t rows, int32_t cols, int64
   if (!in || !out || rows <= 0 || cols <= 0 || ld_in < cols || ld_out < rows) return SDN_E_INVALID;
   hipLaunchKernelGGL(k_transpose16, dim3((cols + 63) / 64, (rows + 63) / 64), dim3(THREADS), 0, (hipStream_t)stream,
                      (const unsigned short*)in, rows, cols, (long)ld_in, (unsigned short*)out, (long)ld_out);
+  return sdn_launch_status();
+}
+
+extern "C" int sdn_transpose32(const void* in, int32_t rows, int32_t cols, int64_t ld_in, void* out, int64_t ld_out,
+                               void* stream) {
+  if (!in || !out || rows <= 0 || cols <= 0 || ld_in < cols || ld_out < rows ||
+      ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 3) || (rows + 63) / 64 > 65535)
+    return SDN_E_INVALID;
+  hipLaunchKernelGGL(k_transpose32, dim3((cols + 63) / 64, (rows + 63) / 64), dim3(THREADS), 0, (hipStream_t)stream,
+                     (const unsigned*)in, rows, cols, (long)ld_in, (unsigned*)out, (long)ld_out);
   return sdn_launch_status();
 }
 

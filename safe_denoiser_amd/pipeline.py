@@ -113,7 +113,8 @@ class SafeDenoiserPipeline:
     @classmethod
     def from_pretrained(cls, model_dir: str, scheduler=None, torch_dtype=torch.bfloat16, variant: str = "threshold_time",
                         latent_repeat: int = 1, tokenizer=None, weights_variant: Optional[str] = None, precision: Optional[str] = None,
-                        device="cuda", text_encoder_precision: Optional[str] = "bf16x3", **kwargs):
+                        device="cuda", text_encoder_precision: Optional[str] = "bf16x3", vae_precision: Optional[str] = None,
+                        **kwargs):
         """`pipeline_func.from_pretrained(model_id, scheduler=scheduler, torch_dtype=weight_dtype, revision="fp16")`
         (run_nudity.py:104-122) for a LOCAL diffusers-layout directory: unet / vae / text_encoder weights (safetensors or
         .bin) are packed into the engine's layouts, `scheduler/scheduler_config.json` is honoured when no scheduler object is
@@ -123,6 +124,10 @@ class SafeDenoiserPipeline:
         `precision="scheduled"` (round 5) = the fp32 RESULT at 1.4 x the 16-bit cost: the fp16 plan and the bf16x3 plan over the
         same weights, the bf16x3 one on the steps inside the repellency window (`precision_schedule=`, default {"window": True};
         DESIGN 10.1), text encoder bf16x3.
+        `vae_precision`: None (default, in every mode above) = the VAE in the 16-bit type; "fp32" / "bf16x3" = its fp32-storage
+        plans (AutoencoderKL(precision=...)), for `decode_latents` and for the encoder behind `driver.build_repellency`.  "fp32" is
+        the arithmetic of the reference's own load (run_nudity.py:277, load_sd(..., torch.float32)); "bf16x3" is within 1e-4 of it
+        per forward.
         `variant` = the gating variant (SD_FUNCTIONS[erase_id], driver.ERASE_IDS); `latent_repeat` = guidance branches that
         share their latents (2 = CFG, 3 = lra / SLD).  `revision` and other hub arguments are accepted and ignored."""
         import os
@@ -150,7 +155,7 @@ class SafeDenoiserPipeline:
         del usd
         vae = enc = None
         if os.path.isdir(os.path.join(model_dir, "vae")):
-            vae = AutoencoderKL(dtype=dt16, **ck.vae_kwargs(ck.read_config(os.path.join(model_dir, "vae"))))
+            vae = AutoencoderKL(dtype=dt16, precision=vae_precision, **ck.vae_kwargs(ck.read_config(os.path.join(model_dir, "vae"))))
             vae.load_state_dict(ck.load_weights(os.path.join(model_dir, "vae"), weights_variant), device=device)
         if os.path.isdir(os.path.join(model_dir, "text_encoder")):
             # the reference loads the text encoder in the pipeline's dtype (run_nudity.py:277: fp32): an fp32 / bf16x3 UNet gets the

@@ -19,7 +19,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
-from ._model import HALF_DTYPES, EngineModel
+from ._model import ALL_DTYPES, EngineModel
 
 SD14_VAE_CONFIG = dict(in_channels=3, out_channels=3, latent_channels=4, block_out_channels=(128, 256, 512, 512),
                        layers_per_block=2, norm_num_groups=32, sample_size=512, scaling_factor=0.18215, shift_factor=0.0,
@@ -80,12 +80,17 @@ class EncoderOutput:
 class AutoencoderKL(EngineModel):
     """AutoencoderKL.  `sample_size` is the IMAGE side (diffusers' meaning); the latent side is
     sample_size / 2**(levels-1).  The object itself is the decoder half; `.encoder_half` (built on first use or when
-    the state_dict carries `encoder.*`) is the same class in the encoder role."""
+    the state_dict carries `encoder.*`) is the same class in the encoder role.
+
+    `dtype=torch.float32` / `precision="fp32"` (exact f32 products) and `precision="bf16x3"` (fp32 storage, split-operand
+    contractions) are the fp32-storage plans (sdn_vae_config.dtype 2 / 3): the reference loads the VAE in fp32 with the rest of the
+    pipeline (run_nudity.py:277).  Inputs and outputs are fp32 NCHW in every mode, so every method below runs unchanged on them;
+    the encoder half inherits the mode."""
 
     MAX_CHUNK = 8                      # images per plan invocation; sdn_vae_* chunk larger batches themselves (32-bit DMA offsets)
 
-    def __init__(self, dtype=torch.bfloat16, _role: str = "decoder", **config):
-        code = self._storage(dtype, None, HALF_DTYPES, "storage dtype must be torch.bfloat16 or torch.float16")
+    def __init__(self, dtype=torch.bfloat16, precision=None, _role: str = "decoder", **config):
+        code = self._storage(dtype, precision, ALL_DTYPES, "storage dtype must be torch.bfloat16, torch.float16 or torch.float32")
         cfg = dict(SD14_VAE_CONFIG)
         cfg.update(config)
         self.config = SimpleNamespace(**cfg)
@@ -95,8 +100,13 @@ class AutoencoderKL(EngineModel):
         if cfg["sample_size"] % self.up_factor:
             raise _lib.SdnError("sample_size must be a multiple of 2**(levels-1)")
         self.latent_size = cfg["sample_size"] // self.up_factor
-        # images per plan invocation: the C side bounds batch * side^2 * max(channels) * 2 bytes by 2^32 (DMA offsets)
-        self.MAX_CHUNK = max(1, min(8, (2 ** 32 - 1) // (cfg["sample_size"] ** 2 * max(boc) * 2)))
+        # images per plan invocation: the C side bounds batch * side^2 * max(channels) * 2 bytes by 2^32 (DMA offsets); the
+        # fp32-storage plans take at most 4 and keep the largest map of a chunk below 2^31 bytes (vae_chunk(), sdn_plan_api.hip)
+        if code >= 2:
+            largest = max((cfg["sample_size"] >> j) ** 2 * max(boc[j], boc[min(j + 1, n - 1)]) * 4 for j in range(n))
+            self.MAX_CHUNK = max(1, min(4, (2 ** 31 - 1) // largest))
+        else:
+            self.MAX_CHUNK = max(1, min(8, (2 ** 32 - 1) // (cfg["sample_size"] ** 2 * max(boc) * 2)))
         c = _lib.VaeConfig(latent_channels=cfg["latent_channels"], out_channels=cfg["out_channels"],
                            sample_size=self.latent_size, n_levels=n,
                            block_out_channels=(C.c_int32 * 4)(*(boc + [0] * (4 - n))),
@@ -118,7 +128,7 @@ class AutoencoderKL(EngineModel):
 
     def _encoder(self):
         if self.encoder_half is None:
-            self.encoder_half = AutoencoderKL(dtype=self.dtype, _role="encoder", **self._user_config)
+            self.encoder_half = AutoencoderKL(dtype=self.dtype, precision=self.precision, _role="encoder", **self._user_config)
         return self.encoder_half
 
     @staticmethod
