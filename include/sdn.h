@@ -546,6 +546,21 @@ int sdn_ffn_geglu_fused(int32_t dtype, int64_t M, int32_t C, const void* x, cons
                         const float* c1, const float* d1, const void* w_cat, const float* b_cat, const void* residual, void* out,
                         float* col_stats, void* stream);
 
+/* The K = 320 linears of the C = 320 transformer blocks on a kernel of their own (k_gemm_k320: weights resident in registers,
+ * activation rows streamed through LDS by persistent workgroups, no tile boundary):
+ *   out[M, N] = A[M, 320] . W[N, 320]^T (+ bias) (+ residual)                      ln_c == ln_d == NULL
+ *   out       = LayerNorm-folded form of sdn_gemm_ln_* with row_stats = NULL       ln_c, ln_d from sdn_ln_fold (no bias / residual)
+ * desc: K == 320, N % 320 == 0, any M, plain A, no activation, 16-bit whole-width output (n_valid 0 or N), ldc 0 or a multiple
+ * of 8 >= N; `residual` [M, ldc] 16-bit is added into the accumulators before the k loop (the sum of sdn_gemm_desc.res_pre = 1).
+ * Everything else is SDN_E_INVALID.  dtype 0 = bf16, 1 = fp16.  Bit-identical to sdn_gemm_* (res_pre = 1 with a residual) /
+ * sdn_gemm_ln_* on the same operands; the generic entries never dispatch to this kernel. */
+int sdn_gemm_k320(int32_t dtype, const sdn_gemm_desc* desc, const void* a, const void* w, const float* bias, const float* ln_c,
+                  const float* ln_d, float ln_eps, const void* residual, void* out, void* stream);
+/* Its workgroup -> (row stream, 320-column group) mapping for a grid of `grid` workgroups: returns the number of row streams
+ * (< 0: bad arguments); *stream_out = -1 for a workgroup that has no work.  The col_groups siblings of a stream share wg % 8,
+ * i.e. an XCD under round-robin dealing.  Host only, no GPU needed. */
+int32_t sdn_gemm_k320_map(int32_t grid, int32_t col_groups, int32_t wg, int32_t* stream_out, int32_t* group_out);
+
 /* GroupNorm statistics without a pass over the tensor: the GEMM that PRODUCES a GroupNorm input also emits, per block of
  * 128 output rows and per column, the (sum, sum of squares) of the 16-bit values it stores -- col_stats [ceil(M/128)][N][2]
  * f32 (sdn_gemm_stats_*: 16-bit output, n_valid == N, no GEGLU, no rowgate) -- and sdn_groupnorm_cols_* reduces those

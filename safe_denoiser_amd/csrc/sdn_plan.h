@@ -67,6 +67,7 @@ struct Op {
   int pair_in = 0;           // bf16x3 plan: attention whose q / k / v are column blocks of ONE hi | lo pair-row buffer (sdn_attention_x3_pairs)
   int tri_out = 0;           // bf16x3 plan: GroupNorm / LayerNorm / attention write the bf16 hi|lo|hi triple a GEMM will read
   int dyn_ldc = 0;           // projected CLIP plan: the output's leading dimension is the call's out2_rs
+  int k320 = 0;              // K = 320 linear of a C = 320 transformer block on its own kernel (sdn_gemm_k320) instead of sdn_gemm_* / sdn_gemm_ln_*
   int n1 = 0, mod = 0, ld_mod = 0, patch = 0;
   // GN / LN / conv_in / attention scalars
   int batch = 0, hw = 0, c1 = 0, c2 = 0, groups = 0, silu = 0;
@@ -183,6 +184,7 @@ struct sdn_unet {
   const void *kv_w = nullptr, *kv_text = nullptr, *kv_ws = nullptr;
   bool x3_pairs = true;                 // bf16x3 plan: self-attention on pre-split operands (qkv projection writes hi | lo pair rows)
   bool res_pre = true;                  // attention output projections: residual into the accumulators before the k loop (sdn_gemm_desc.res_pre)
+  bool gemm_k320 = true;                // sdn_debug_set_gemm_k320: the K = 320 linears of the C = 320 transformer blocks (16-bit plans) on k_gemm_k320
   bool x3_expand = true;                // dtype 3: GEMM operands as bf16 triples on the LDS-DMA tiles (false: the f32-staging k_gemm_x3 everywhere)
   bool split_k = false;                 // sdn_unet_set_split_k: small-M GEMMs of the plan take the split-K form (off by
                                         // default: it changes fp32 summation order with the batch size, and batch rows are
@@ -224,6 +226,10 @@ struct sdn_unet {
 
 namespace sdn_plan {
 
+// Which forms of the K = 320 linears Builder::transformer_body puts on k_gemm_k320 (sdn_gemm_k320.hip): decided per variant from the
+// measured table of DESIGN 10.20 -- a form that measures slower than k_gemm_dma stays there.
+constexpr bool kK320Plain = true, kK320Ln = true, kK320Rp = true;
+
 // Emits one plan: every method appends ops to `plan` and allocates / releases activations in `arena`.  The shared emitters live in
 // sdn_plan_core.hip, the per-model blocks and build_*() in sdn_plan_unet / _mmdit / _vae / _text.hip.
 struct Builder {
@@ -242,6 +248,7 @@ struct Builder {
   Ref pending_cols;                    // set by want_stats() for the NEXT emitted GEMM
   int64_t kv_top = 0;             // bytes of persistent text K / V slots handed out so far (space SP_KV)
   bool res_pre_next = false;      // the next gemm() adds its residual into the accumulators before the k loop (sdn_gemm_desc.res_pre)
+  bool k320_next = false;         // the next gemm() / gemm_ln() may go to sdn_gemm_k320 (set by transformer_body for the C = 320 projections)
   bool triple_out_next = false;   // the next gemm() writes the triple of its result (its only reader is another x3 GEMM)
   bool pair_out_next = false;     // the next gemm() writes hi | lo pair rows (a projection whose only reader is sdn_attention_x3_pairs)
   bool plan_bad = false;          // an emitter met an inconsistency: the finished plan gets ws_bytes = -1

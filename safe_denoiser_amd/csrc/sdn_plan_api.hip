@@ -385,6 +385,9 @@ void sdn_debug_set_x3_expand(sdn_unet* u, int on) { if (u && u->x3_expand != (on
 
 void sdn_debug_set_res_pre(sdn_unet* u, int on) { if (u && u->res_pre != (on != 0)) set_plan_toggle(u, &sdn_unet::res_pre, on != 0); }
 
+// the K = 320 linears of the C = 320 transformer blocks on k_gemm_k320 (1, default) or on k_gemm_dma (0): A/B and equality tests
+void sdn_debug_set_gemm_k320(sdn_unet* u, int on) { if (u && u->gemm_k320 != (on != 0)) set_plan_toggle(u, &sdn_unet::gemm_k320, on != 0); }
+
 // run the BasicTransformerBlock LayerNorms as separate kernels again (the derived regions stay)
 void sdn_debug_set_ln_fold(sdn_unet* u, int on) { if (u) set_plan_toggle(u, &sdn_unet::ln_fold, on != 0); }
 

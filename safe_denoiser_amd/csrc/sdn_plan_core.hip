@@ -107,6 +107,7 @@ void Builder::gemm(int64_t M, int N, int K, Ref a, Ref w, Ref bias, Ref out, int
                    int rows_per_batch, int ld_rowbias) {
   const bool forced = force_x3t_next && x3t && !x3t_hold;
   force_x3t_next = false;
+  if (x3t) k320_next = false;
   if ((x3t_on(a) || forced) && (act_ == SDN_ACT_NONE || act_ == SDN_ACT_GEGLU) && out_kind != SDN_OUT_F32_NCHW && n_valid == 0) {
     // A' = [hi | lo | hi] (written by the producing GroupNorm / LayerNorm / attention / GEGLU epilogue, or by a split pass),
     // W' = [hi | hi | lo]: one bf16 GEMM with three times the k loop; F32 residual, F32 (or, for GEGLU, triple) output
@@ -131,6 +132,8 @@ void Builder::gemm(int64_t M, int N, int K, Ref a, Ref w, Ref bias, Ref out, int
     return;
   }
   triple_out_next = false; pair_out_next = false;
+  const bool k320_ok = k320_next;
+  k320_next = false;
   const bool rp = res_pre_next && residual.space != SP_NONE && act_ == SDN_ACT_NONE && out_kind == SDN_OUT_BF16 && n_valid == 0 && es == 2;
   res_pre_next = false;
   Op o; o.kind = OP_GEMM; memset(&o.gd, 0, sizeof(o.gd));
@@ -143,6 +146,13 @@ void Builder::gemm(int64_t M, int N, int K, Ref a, Ref w, Ref bias, Ref out, int
   o.bytes = 2.0 * ((double)M * K + (double)N * K + (double)M * (act_ == SDN_ACT_GEGLU ? N / 2 : N)) +
             (residual.space != SP_NONE ? 2.0 * (double)M * N : 0.0);
   snprintf(o.label, sizeof(o.label), "k_gemm<%d>%s", sdn_gemm_pick_tile((int)M, N, K, act_, residual.space != SP_NONE && !rp), rp ? "/rp" : "");
+  // the forms sdn_gemm_k320 takes: bias and a pre-added residual at most, whole-width 16-bit output, no column statistics
+  if (k320_ok && K == 320 && N % 320 == 0 && act_ == SDN_ACT_NONE && out_kind == SDN_OUT_BF16 && n_valid == 0 && a2.space == SP_NONE &&
+      rowbias.space == SP_NONE && (residual.space == SP_NONE || rp) && pending_cols.space == SP_NONE && !u->split_k &&
+      (rp ? kK320Rp : kK320Plain)) {
+    o.k320 = 1;
+    snprintf(o.label, sizeof(o.label), "k_gemm_k320%s", rp ? "/rp" : "");
+  }
   push_gemm(o);
 }
 // Small-M / long-K GEMMs (one-prompt batches) run in split-K form: the partial buffer lives only for this op.

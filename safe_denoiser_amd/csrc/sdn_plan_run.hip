@@ -207,6 +207,11 @@ static int launch_op_16(const sdn_unet* u, const Op& o, const Call& P, bool f16,
                                (void*)P(o.out), stream);
       break;
     case OP_GEMM:
+      if (o.k320) {
+        rc = sdn_gemm_k320(f16 ? 1 : 0, &o.gd, P(o.a), P(o.w), o.ln ? nullptr : (const float*)P(o.bias), o.ln ? (const float*)P(o.ln_c) : nullptr,
+                           o.ln ? (const float*)P(o.ln_d) : nullptr, o.eps, o.ln ? nullptr : P(o.residual), (void*)P(o.out), stream);
+        break;
+      }
       if (o.dyn_ldc) {
         sdn_gemm_desc gd = o.gd; gd.ldc = (int)P.out2_rs;
         rc = (f16 ? sdn_gemm_f16 : sdn_gemm_bf16)(&gd, P(o.a), nullptr, P(o.w), nullptr, nullptr, nullptr, nullptr, (void*)P(o.out), stream);

@@ -51,6 +51,11 @@ void Builder::gemm_ln(const Act& x, int64_t rows, int N, int K, const std::strin
   { int t = sdn_gemm_pick_tile((int)rows, N, K, act_);
     if (t == 8 && N % 320 == 0) t = 10;                        // (sdn_gemm_impl: the folded forms have no 256-wide instantiation)
     snprintf(o.label, sizeof(o.label), "k_gemm<%d>/ln%d", t, prepass ? 2 : 1); }   // /lnL: L = the symbol's LNF
+  if (k320_next && !prepass && K == 320 && N % 320 == 0 && act_ == SDN_ACT_NONE && pending_cols.space == SP_NONE && kK320Ln) {
+    o.k320 = 1;                                                // statistics from the fragments, as LNF = 1: sdn_gemm_k320
+    snprintf(o.label, sizeof(o.label), "k_gemm_k320/ln1");
+  }
+  k320_next = false;
   plan->ops.push_back(o);
   plan->flops += o.flops;
   if (prepass) drop(st);
@@ -141,6 +146,10 @@ void Builder::transformer_body(const std::string& pfx, Act& x, const Act& out, i
   Act gn = act(rows, C, hw, x.side);
   groupnorm(x, nullptr, 1e-6f, 0, ng, nb, gn);
   Act h = act(rows, C, hw, x.side);
+  // the five K = 320 linears of a C = 320 block (16-bit plans, whole batch) run on k_gemm_k320: proj_in, qkv,
+  // attn1.to_out, attn2.to_q, attn2.to_out -- same bits as the k_gemm_dma launches they replace
+  const bool k320 = u->gemm_k320 && C == 320 && es == 2 && !x3t && u->subbatch_bytes == 0;
+  k320_next = k320;
   gemm(rows, C, C, R(gn), piw, pib, R(h));
   drop(gn);
   // LayerNorm folding (gemm_ln): measured per shape (tools/bench_lnfold.py) -- it pays at C = 320 / 640 for the
@@ -153,6 +162,7 @@ void Builder::transformer_body(const std::string& pfx, Act& x, const Act& out, i
   Act ln;
   if (!fold12 || !fold3) ln = act(rows, C, hw, x.side);
   Act qkvb = act(rows, 3 * C, hw, x.side);
+  k320_next = k320;
   if (fold12) {
     gemm_ln(h, rows, 3 * C, C, tb + ".attn1.to_q.weight", qkv, l1g, l1b, Ref(), R(qkvb), SDN_ACT_NONE, 3 * C > 960 || u->ln_prepass_all);
   } else {
@@ -167,10 +177,12 @@ void Builder::transformer_body(const std::string& pfx, Act& x, const Act& out, i
   drop(qkvb);
   Act h2 = act(rows, C, hw, x.side);
   res_pre_next = u->res_pre;
+  k320_next = k320;
   gemm(rows, C, C, R(at), o1w, o1b, R(h2), SDN_ACT_NONE, R(h));
   drop(h);
   // cross-attention
   Act qb = act(rows, C, hw, x.side);
+  k320_next = k320;
   if (fold12) {
     gemm_ln(h2, rows, C, C, tb + ".attn2.to_q.weight", q2w, l2g, l2b, Ref(), R(qb), SDN_ACT_NONE, u->ln_prepass_all != 0);
   } else {
@@ -209,6 +221,7 @@ void Builder::transformer_body(const std::string& pfx, Act& x, const Act& out, i
   }
   Act h3 = act(rows, C, hw, x.side);
   res_pre_next = u->res_pre;
+  k320_next = k320;
   gemm(rows, C, C, R(at), o2w, o2b, R(h3), SDN_ACT_NONE, R(h2));
   drop(h2); drop(at);
   // GEGLU feed-forward

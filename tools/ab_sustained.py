@@ -27,7 +27,10 @@ for rnd in range(3):
         elif os.environ.get("LNPRE") == "1":                     # second arm = every folded LayerNorm's row statistics from the pre-pass (LNF = 2 kernels)
             import ctypes as C
             sda.lib().sdn_debug_set_ln_prepass_all(C.c_void_p(u._h.value), 1 if v else 0)
-        elif os.environ.get("UP4") == "1":                       # second arm = upsampler convs as the nine-tap op (sdn_unet_set_conv_up4 off)
+        elif os.environ.get("K320") == "1":                      # second arm = the K = 320 linears of the C = 320 blocks on k_gemm_dma (sdn_debug_set_gemm_k320 off)
+            import ctypes as C
+            sda.lib().sdn_debug_set_gemm_k320(C.c_void_p(u._h.value), 0 if v else 1)
+        elif os.environ.get("UP4") == "1":                      # second arm = upsampler convs as the nine-tap op (sdn_unet_set_conv_up4 off)
             u.set_conv_up4(not v)
         elif TEXTVER:
             u.set_text_version(5 if v else 0)
