@@ -752,8 +752,8 @@ int sdn_copy_rows_strided(const void* src, int32_t batch, int32_t rows_per_batch
  * 64 (588 -> 640): the convolution is sdn_clip_patch_rows followed by an ordinary plan GEMM. */
 typedef struct sdn_clip_vision_config {
   int32_t image_size, patch_size;        /* 224, 14; image_size % patch_size == 0                      */
-  int32_t hidden_size, intermediate_size;/* 1024, 4096; both % 128 == 0, hidden <= 1280                */
-  int32_t num_layers, num_heads;         /* 24, 16 (head dim must be 64)                               */
+  int32_t hidden_size, intermediate_size;/* 1024, 4096 (ViT-H: 1280, 5120); both % 128 == 0, hidden <= 1280 */
+  int32_t num_layers, num_heads;         /* 24, 16; head dim 64 (ViT-L/14) or 80 (ViT-H/14: 1280, 16)  */
   int32_t projection_dim;                /* 768; % 32 == 0                                             */
   int32_t act;                           /* SDN_ACT_QUICK_GELU (OpenAI CLIP) or SDN_ACT_GELU           */
   int32_t dtype;                         /* 0 = bf16, 1 = fp16 storage (the reference runs this model in fp16); 2 / 3 (fp32
@@ -806,6 +806,19 @@ int sdn_clip_normalize_u8(const uint8_t* in, int32_t batch, int32_t size, float 
 int sdn_embed_row_scores(const void* x, int32_t dtype_x, int64_t ldx, const void* y, int32_t dtype_y, int64_t ldy,
                          int32_t y_rows, int32_t rows, int32_t dim, int32_t normalize_y, float scale, float bias,
                          float* out, void* stream);
+/* The COCO driver's CLIP-score head (run_coco30k.py:217-234, Eval.clip_score, and :191-215, measure_similarity): the mean of the
+ * WHOLE cosine matrix, `(normalize(X) @ normalize(Y).T).mean()`, as one f32 scalar on the device:
+ *   out[0] = (sum_i x_i / |x_i|) . (sum_j y_j / |y_j|) / (rx ry)
+ * -- the rx x ry matrix is never formed.  x: [rx, dim] of dtype_x (0 bf16, 1 fp16, 2 f32), row pitch ldx ELEMENTS; y: [ry, dim]
+ * likewise: the operand contract of sdn_embed_row_scores (16-byte aligned bases; a pitch that is a multiple of 16 bytes, or a single
+ * row, selects the vector loads; nothing at or past column dim of a row is read).  scratch: f32 [2, dim], contents ignored and
+ * overwritten (the two sums of normalised rows).  Two launches: one workgroup per matrix takes the rows' norms (one wave per row,
+ * four rows at a time) and adds the normalised rows to its sum in row order, then one workgroup forms the dot product.  No atomics:
+ * the same operands give the same bits on every run.  Every accumulation is f32.  A zero-norm row yields NaN, as the torch
+ * expression does.  No allocation, no synchronisation.  SDN_E_INVALID: a null pointer, dim < 1, rx < 1, ry < 1, a pitch below dim,
+ * a dtype code outside 0..2, x or y not 16-byte aligned, scratch or out not 4-byte aligned, dim, rx or ry above 2^30. */
+int sdn_embed_cross_mean(const void* x, int32_t dtype_x, int64_t ldx, int32_t rx, const void* y, int32_t dtype_y, int64_t ldy,
+                         int32_t ry, int32_t dim, float* scratch, float* out, void* stream);
 /* The transform of the negative reference images (data/dataloader.py:46-78: `transforms.Resize((512, 512))` on a PIL image =
  * `Image.resize((512, 512), BILINEAR)`, then ToTensor and Normalize(.5, .5)), for a batch of equally sized RGB images of ANY
  * aspect ratio.

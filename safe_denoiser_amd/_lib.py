@@ -220,6 +220,7 @@ SIGNATURES = {
     "sdn_resize_bilinear_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp]),
     "sdn_spatial_mean_f32": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "sdn_embed_row_scores": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp]),
+    "sdn_embed_cross_mean": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp]),
     "sdn_t5_create": (C.c_int, [C.POINTER(T5Config), C.POINTER(_vp)]),
     "sdn_t5_workspace_bytes": (_sz, [_vp, _i32, _i32]),
     "sdn_t5_flops": (C.c_double, [_vp, _i32, _i32, C.POINTER(C.c_double)]),

@@ -161,13 +161,29 @@ def clip_vision_kwargs(cfg: dict) -> dict:
     for k in ("image_size", "patch_size", "hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "projection_dim"):
         if not isinstance(cfg.get(k), int):
             raise NotImplementedError(f"vision tower: config value {k} = {cfg.get(k)!r} is not implemented by the engine's plan (needs an integer)")
-    if cfg["hidden_size"] != 64 * cfg["num_attention_heads"]:
+    if cfg["hidden_size"] not in (64 * cfg["num_attention_heads"], 80 * cfg["num_attention_heads"]):
         raise NotImplementedError(f"vision tower: hidden_size = {cfg['hidden_size']} with {cfg['num_attention_heads']} heads is not "
-                                  "implemented by the engine's plan (needs heads of 64)")
+                                  "implemented by the engine's plan (needs heads of 64 or 80)")
     _require(cfg, "vision tower", layer_norm_eps=1e-5, attention_dropout=0.0, num_channels=3)
     keys = ("image_size", "patch_size", "hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "projection_dim",
             "hidden_act")
     return {k: cfg[k] for k in keys}
+
+
+def clip_model_text_kwargs(cfg: dict) -> dict:
+    """CLIPTextModelWithProjection(**kwargs) from the config.json of a whole transformers CLIPModel: its `text_config` with the
+    top-level `projection_dim`.  (clip_projection_kwargs stays the reader of a stand-alone text_encoder/config.json.)"""
+    arch = cfg.get("architectures")
+    if arch is not None and list(arch) != ["CLIPModel"]:
+        raise NotImplementedError(f"CLIPModel text tower: only architectures = ['CLIPModel'] is implemented, got {arch!r}")
+    if not isinstance(cfg.get("text_config"), dict):
+        raise NotImplementedError("CLIPModel text tower: config.json has no text_config")
+    t = dict(cfg["text_config"])
+    if "projection_dim" in cfg:
+        t["projection_dim"] = cfg["projection_dim"]
+    t.pop("architectures", None)
+    t["architectures"] = ["CLIPTextModelWithProjection"]            # the text half of a CLIPModel is that model's arithmetic
+    return clip_projection_kwargs(t)
 
 
 def t5_kwargs(cfg: dict) -> dict:

@@ -10,7 +10,8 @@ torchvision's Resize(224, BICUBIC) + CenterCrop + ToTensor + Normalize on a PIL 
 followed by ((u8 / 255) - mean) / std, and Pillow's 8-bit resize is integer arithmetic that sdn_image_resize_u8 reproduces bit for
 bit from coefficient tables built here in double (resize_tables).  Non-square inputs are refused there; resize_rect /
 resize_rect_u8 (sdn_image_resize_rect_u8) resample images of any aspect ratio with Pillow's bilinear or bicubic filter -- the
-transform of the negative reference images (safe_denoiser_amd/data.py).
+transform of the negative reference images (safe_denoiser_amd/data.py) -- and clip_preprocess_any is CLIP's preprocessing for any
+aspect ratio (shortest side to 224, centre crop), computing only the crop window.
 """
 from __future__ import annotations
 
@@ -27,6 +28,9 @@ from ._model import HALF_DTYPES, EngineModel
 
 VIT_L14_CONFIG = dict(image_size=224, patch_size=14, hidden_size=1024, intermediate_size=4096, num_hidden_layers=24,
                       num_attention_heads=16, projection_dim=768, hidden_act="quick_gelu")
+# laion/CLIP-ViT-H-14-laion2B-s32B-b79K, the COCO driver's evaluator (run_coco30k.py:177-182): 16 heads of 80
+VIT_H14_CONFIG = dict(image_size=224, patch_size=14, hidden_size=1280, intermediate_size=5120, num_hidden_layers=32,
+                      num_attention_heads=16, projection_dim=1024, hidden_act="gelu")
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)                   # clip.preprocess's Normalize
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 PRECISION_BITS = 22                                                # Pillow: 32 - 8 - 2
@@ -201,6 +205,113 @@ def clip_preprocess(images, size: int = 224, device="cuda") -> torch.Tensor:
     return parts[0] if len(parts) == 1 else torch.cat(parts)
 
 
+# ---- any aspect ratio: shortest side to `size`, centre crop ------------------------------------------------------------------------
+CROP_RULES = ("transformers", "torchvision")
+
+
+def resized_shape(h: int, w: int, size: int) -> tuple:
+    """(height, width) after `resize(shortest_edge=size)`: the short side becomes `size`, the long one int(size * long / short)
+    (transformers' get_resize_output_image_size and torchvision's Resize(int) agree on this)."""
+    short, long = (w, h) if w <= h else (h, w)
+    new_long = int(size * long / short)
+    return (new_long, size) if w <= h else (size, new_long)
+
+
+def crop_offset(length: int, size: int, crop: str = "transformers") -> int:
+    """First kept index of a centre crop of `size` out of `length` >= size.  transformers' center_crop: (length - size) // 2.
+    torchvision's CenterCrop: int(round((length - size) / 2.0)) with Python's round (half to even) -- written from its source;
+    torchvision is not installed where this was developed, so that rule is UNVERIFIED against the library.  The two differ when
+    the excess is odd and (excess - 1) / 2 is odd."""
+    if crop not in CROP_RULES:
+        raise _lib.SdnError(f"crop must be one of {CROP_RULES}, got {crop!r}")
+    if length < size:
+        raise _lib.SdnError(f"cannot crop {size} out of {length}")
+    return (length - size) // 2 if crop == "transformers" else int(round((length - size) / 2.0))
+
+
+def crop_tables(n_in: int, n_res: int, off: int, size: int, filter: str = "bicubic"):
+    """One axis of resize-then-crop as ONE table set for sdn_image_resize_rect_u8 with `size` outputs: rows [off, off + size) of
+    resize_tables(n_in, n_res) -- each output of Pillow's pass depends on its own taps only, so the cropped resize is bit for bit
+    the crop of the resize.  An axis Pillow does not resample (n_res == n_in) gets the one-tap table of weight 2^22 at off + i,
+    which reproduces the source byte ((2^21 + 2^22 u) >> 22 = u), or None when nothing is cropped either (no pass at all)."""
+    if n_res == n_in:
+        if n_in == size:
+            return None
+        coeffs = np.full((size, 1), 1 << PRECISION_BITS, dtype=np.int32)
+        bounds = np.stack([np.arange(off, off + size, dtype=np.int32), np.ones(size, dtype=np.int32)], axis=1)
+        return coeffs, np.ascontiguousarray(bounds), 1
+    coeffs, bounds, ksize = resize_tables(n_in, n_res, filter)
+    return np.ascontiguousarray(coeffs[off:off + size]), np.ascontiguousarray(bounds[off:off + size]), ksize
+
+
+def _device_crop_tables(n_in: int, n_res: int, off: int, size: int, device):
+    key = ("crop", n_in, n_res, off, size, str(device))
+    if key not in _TABLES:
+        t = crop_tables(n_in, n_res, off, size)
+        _TABLES[key] = (None, None, 0) if t is None else (torch.from_numpy(t[0]).to(device), torch.from_numpy(t[1]).to(device), t[2])
+    return _TABLES[key]
+
+
+def _as_u8_groups(images, device):
+    """uint8 device tensors [b, H, W, 3] in input order, any H and W: the tensor itself, or the PIL images grouped by runs of equal
+    size (one launch per run)."""
+    if isinstance(images, torch.Tensor):
+        t = images
+        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3:
+            raise _lib.SdnError(f"images must be uint8 [B, H, W, 3], got {t.dtype} {tuple(t.shape)}")
+        return [t.to(device).contiguous()]
+    out, run = [], []
+    for im in list(images):
+        if not hasattr(im, "size") or not hasattr(im, "convert"):
+            raise _lib.SdnError("images must be a uint8 tensor [B, H, W, 3] or a list of PIL images")
+        a = np.asarray(im.convert("RGB"), dtype=np.uint8)
+        if run and run[-1].shape != a.shape:
+            out.append(torch.from_numpy(np.stack(run)).to(device))
+            run = []
+        run.append(a)
+    if run:
+        out.append(torch.from_numpy(np.stack(run)).to(device))
+    return out
+
+
+def clip_preprocess_any(images, size: int = 224, crop: str = "transformers", device="cuda") -> torch.Tensor:
+    """CLIP's preprocessing for images of ANY aspect ratio: a list of PIL images (any sizes) or a uint8 tensor [B, H, W, 3] ->
+    pixel_values f32 [B, 3, size, size] on the GPU.  The shortest side is resized to `size` with Pillow's bicubic filter (the long
+    side to int(size * long / short)), the centre `size` x `size` is cropped, and ((u8 / 255) - CLIP_MEAN) / CLIP_STD is taken.
+    Only the crop is computed (crop_tables), bit for bit Pillow's resize followed by the crop.
+    crop = "transformers" (default): CLIPImageProcessor's rule, what CLIPProcessor applies on the reference's `coco` path;
+    crop = "torchvision": CenterCrop's rule (open_clip's transform) -- unverified against the library, see crop_offset."""
+    _lib.require_gpu()
+    if crop not in CROP_RULES:
+        raise _lib.SdnError(f"crop must be one of {CROP_RULES}, got {crop!r}")
+    if isinstance(images, torch.Tensor) and images.is_cuda:
+        device = images.device
+    parts = []
+    for t in _as_u8_groups(images, device):
+        b, h, w = t.shape[0], t.shape[1], t.shape[2]
+        if b == 0:
+            continue
+        rh, rw = resized_shape(h, w, size)
+        top, left = crop_offset(rh, size, crop), crop_offset(rw, size, crop)
+        if (rh != h and h == size) or (rw != w and w == size):
+            # an axis that is resampled although it already has `size` entries (an upscale of an image whose LONG side is `size`):
+            # the rectangular resize takes no table for an axis that keeps its length, so resize in full and crop
+            u8 = resize_rect(t, (rh, rw), "bicubic")[0][:, top:top + size, left:left + size].contiguous()
+            parts.append(normalize_u8(u8))
+            continue
+        cx, bx, kx = _device_crop_tables(w, rw, left, size, t.device)
+        cy, by, ky = _device_crop_tables(h, rh, top, size, t.device)
+        tmp = torch.empty((b, h, size, 3), dtype=torch.uint8, device=t.device) if cx is not None and cy is not None else None
+        f32 = torch.empty((b, 3, size, size), dtype=torch.float32, device=t.device)
+        _lib.check(_lib.lib().sdn_image_resize_rect_u8(t.data_ptr(), b, h, w, size, size, _lib.dptr(cx), _lib.dptr(bx), kx, _lib.dptr(cy),
+                                                       _lib.dptr(by), ky, _lib.dptr(tmp), None, f32.data_ptr(), *CLIP_MEAN, *CLIP_STD,
+                                                       _lib.stream_ptr()), "sdn_image_resize_rect_u8")
+        parts.append(f32)
+    if not parts:
+        return torch.empty((0, 3, size, size), dtype=torch.float32, device=device)
+    return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
 # ---- the tower ------------------------------------------------------------------------------------------------------------------
 class VisionOutput(tuple):
     """(image_embeds, last_hidden_state) with attribute access, like transformers' CLIPVisionModelOutput."""
@@ -239,7 +350,7 @@ def convert_openai_state_dict(sd: dict) -> dict:
 class CLIPVisionModelWithProjection(EngineModel):
     def __init__(self, dtype=torch.float16, **config):
         """dtype = fp16 (the reference's: clip.load on a GPU) or bf16 storage; config = transformers' CLIPVisionConfig fields
-        (defaults: ViT-L/14)."""
+        (defaults: ViT-L/14; VIT_H14_CONFIG is ViT-H/14).  Heads of 64 or of 80."""
         code = self._storage(dtype, None, HALF_DTYPES,
                              "storage dtype must be torch.float16 or torch.bfloat16 (the fp32-storage plans are not built for this model)")
         cfg = dict(VIT_L14_CONFIG)

@@ -97,7 +97,14 @@ __device__ __forceinline__ const unsigned short* row_ptr(const unsigned short* p
 // BIAS (T5 self-attention): scores = scale Q K^T + bias[head, key - query], a Toeplitz bias held as one vector per head in LDS.
 // T5 scores are not scaled by 1 / sqrt(d) and trained biases reach tens, so neither the offset-free bf16 form nor the fp16 form
 // centred on the first tile is sound here: both dtypes take the classic running-maximum loop (as every masked fp16 instance does).
-template <typename T, int HD, bool SEG, bool MASK = false, bool DMA = !SEG, int QS = 1, bool BIAS = false>
+// EXACT (bf16, unmasked single-stream key sets short of one tile, every head dimension): Q stays as stored and the scale is applied to
+// the fp32 scores, p = 2^(s c - m c), in the classic running-maximum loop.  Folding scale * log2(e) into Q re-rounds every element of Q
+// to the storage type, which moves each score by up to 2 u sum_i |q_i k_i| scale; over hundreds of keys those shifts average out in
+// sum_j p_j ds_j (v_j - out), over a few keys they do not: measured per element against float64 at 17 keys and d = 80, bf16 is at 1.10
+// of the budget (half an ulp + (2 u + 2^-13) sum p |v|) with the folded scale and at 0.68 with this form.  fp16 (u eight times
+// smaller, 0.82 with the folded scale) keeps its centred forms.  Such launches are bound by latency, not by vector issue, so the FMA
+// per score that the folded forms exist to save costs nothing there.
+template <typename T, int HD, bool SEG, bool MASK = false, bool DMA = !SEG, int QS = 1, bool BIAS = false, bool EXACT = false>
 __global__ void __launch_bounds__(THREADS)
 k_attn(const AttnArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -106,7 +113,8 @@ k_attn(const AttnArgs a) {
   constexpr int NDB = (HD + 31) / 32;         // 32-row blocks of O^T
   constexpr bool ONES = (HD % 32) != 0;       // a free padding column exists -> row sums via MFMA
   static_assert(!BIAS || (MASK && DMA && QS == 1), "the biased form extends the masked single-buffer instance");
-  constexpr bool OFFSET_FREE = T::kDtype == 0 && !BIAS; // bf16 has fp32's exponent range: softmax without max subtraction (below)
+  static_assert(!EXACT || (!SEG && !MASK && !BIAS && DMA && QS == 1), "the exact-scale form is the plain single-buffer instance");
+  constexpr bool OFFSET_FREE = T::kDtype == 0 && !BIAS && !EXACT; // bf16 has fp32's exponent range: softmax without max subtraction (below)
   // fp16 with a FREE padding column in the Q K^T contraction (d = 40 -> 48) and LDS-DMA tiles -- round 5.  fp16's P needs p < 2^16,
   // so the bf16 form (no offset at all) is out; the classic form pays one FMA + 1/2 v_max3 per score that the bf16 loop does not
   // (VALU is this kernel's bound: 31.4 vs 23.5 ms per forward at B = 192).  Here the scale is folded into Q as for bf16 and the
@@ -114,12 +122,12 @@ k_attn(const AttnArgs a) {
   // column HD of the Q fragment is set to -m0 after tile 0, so the MFMA itself delivers s - m0 for all later tiles -- no per-score
   // subtraction, no running maximum.  p <= 2^15 is checked afterwards through the row sum (sum >= p); a workgroup with a query
   // outside [2^-10, 2^15] re-runs its block with the guarded (running-maximum) loop.
-  constexpr bool CENTRED = T::kDtype == 1 && !SEG && !MASK && DMA && (KQ * 16 > HD);
+  constexpr bool CENTRED = T::kDtype == 1 && !SEG && !MASK && DMA && (KQ * 16 > HD) && !EXACT;
   // The other unmasked fp16 instances (d = 64 / 80 / 160: no free column) take the same idea with the subtraction spelled out:
   // p = 2^(s - m0), one v_sub per score (what the classic form's FMA cost) but no running maximum (16 v_max3, a cross-half swap, two
   // ballots and the conditional rescale per query set and tile), checked and re-run the same way.  MMDiT's joint attention
   // (d = 64, 18-38 % of the SD-v3 forward) is bound by vector issue: 640 vs 512 cycles per 64-key tile and query set.
-  constexpr bool CENTRED_SUB = T::kDtype == 1 && !MASK && !CENTRED;
+  constexpr bool CENTRED_SUB = T::kDtype == 1 && !MASK && !CENTRED && !EXACT;
   constexpr bool QSCALED = OFFSET_FREE || CENTRED || CENTRED_SUB;
   static_assert(!CENTRED || ((HD % 32) != 0 && HD - 16 * (KQ - 1) == 8), "centred form: row sums by the ones column, column HD = element 0 of the h = 1 lanes");
   constexpr int CH = HD / 8;                  // valid 16-B chunks per K / V row
@@ -551,7 +559,7 @@ k_attn(const AttnArgs a) {
       for (int i = 0; i < 16; ++i) ps += st[qs][0][i] + st[qs][1][i];
       l_run[qs] += ps;
     }
-    } else {                                          // fp16: classic running-max form (fp16 P needs p <= 1)
+    } else {                                          // classic running-max form (masked fp16: P needs p <= 1; BIAS; EXACT)
     const float cc = BIAS ? 1.f : a.c;             // (the biased scores are already in log2 units)
     const float m_new = fmaxf(m_run[qs], mx);
     const float mc = m_new * cc;
@@ -1041,6 +1049,12 @@ int launch(const AttnArgs& a, int batch, int heads, hipStream_t st) {
         AttnArgs a2 = a;
         a2.nqb = (a.nq + 2 * QB - 1) / (2 * QB);
         hipLaunchKernelGGL((k_attn<T, HD, false, false, true, 2>), dim3(a2.nqb * a2.npairs), dim3(THREADS), 0, st, a2);
+        return sdn_launch_status();
+      }
+    }
+    if constexpr (T::kDtype == 0) {               // bf16, short of one key tile: the scale stays out of Q (see EXACT)
+      if (a.nk < KV) {
+        hipLaunchKernelGGL((k_attn<T, HD, false, false, true, 1, false, true>), dim3(a.nqb * a.npairs), dim3(THREADS), 0, st, a);
         return sdn_launch_status();
       }
     }

@@ -86,11 +86,13 @@ using namespace sdn_plan;
 
 extern "C" int sdn_clip_vision_create(const sdn_clip_vision_config* cfg, sdn_unet** out) {
   if (!cfg || !out) return SDN_E_INVALID;
-  // widths: the projected CLIP text plan's rules (its ceiling, bigG's 1280, covers ViT-L's 1024); at most 4096 patches
+  // widths: the projected CLIP text plan's rules (its ceiling, bigG's 1280, covers ViT-L's 1024 and ViT-H's 1280); at most 4096
+  // patches; heads of 64 (ViT-L) or 80 (ViT-H): the two head dimensions of the unmasked 16-bit attention kernel a ViT uses
+  const bool head_ok = cfg->num_heads > 0 && (cfg->hidden_size == (int64_t)64 * cfg->num_heads || cfg->hidden_size == (int64_t)80 * cfg->num_heads);
   if (cfg->image_size <= 0 || cfg->patch_size <= 0 || cfg->patch_size > 64 || cfg->image_size % cfg->patch_size != 0 ||
       cfg->image_size / cfg->patch_size > 64 || cfg->hidden_size <= 0 || cfg->hidden_size % 128 != 0 || cfg->hidden_size > 1280 ||
       cfg->intermediate_size <= 0 || cfg->intermediate_size % 128 != 0 || cfg->num_layers <= 0 || cfg->num_heads <= 0 ||
-      cfg->hidden_size != 64 * cfg->num_heads || cfg->projection_dim <= 0 || cfg->projection_dim % 32 != 0 ||
+      !head_ok || cfg->projection_dim <= 0 || cfg->projection_dim % 32 != 0 ||
       (cfg->act != SDN_ACT_QUICK_GELU && cfg->act != SDN_ACT_GELU) || cfg->dtype < 0 || cfg->dtype > 1)
     return SDN_E_INVALID;                                       // (dtype 2 / 3, the fp32-storage modes, are not built yet)
   sdn_unet* u = new sdn_unet();

@@ -15,7 +15,9 @@ Configuration, in the reference's own order (run_nudity.py:534-625):
 Artefacts (run_nudity.py:249-262,466-529; main_utils.py:24-36,74-90), per output directory:
   logs.txt (print + logging file handler), {safe,unsafe,all}/{case}_{'-'.join(categories)}.png (artists: all/{case}.png),
   detect_dict.json ({"unsafe": [...], "toxic_ratio": {...}, "toxic_pred_ratio": {...}, "toxic_size": {...}}), and the
-  merged config.yaml ({**vars(args), **task_config}).  The NudeNet classifier behind `eval_func` is out of scope (SURVEY
+  merged config.yaml ({**vars(args), **task_config}).  A `coco` job (parse_coco_args; run_coco30k.py:483-485,509,529-539) writes
+  all/{case}.png only, logs `CLIP Score (Img, Prompt) is : ...` per case and puts avg_clip / total_imgs into detect_dict.json; its
+  evaluator is safe_denoiser_amd.coco_eval.CocoClipEval.  The NudeNet classifier behind `eval_func` is out of scope (SURVEY
   section 2 #14): `RunArtifacts.record` takes its verdict from a caller-supplied callable.
 Multi-GPU: rank r of W writes under `{save_dir}/rank{r:02d}` (W > 1) so that ranks never share a file; case numbers are
 global, so the union of the rank directories is the reference's single tree.
@@ -80,8 +82,9 @@ def load_yaml(file_path: str) -> dict:
         return yaml.load(f, Loader=yaml.FullLoader)
 
 
-def build_parser(cfg: Mapping[str, Any]) -> argparse.ArgumentParser:
-    """The second-phase parser of run_nudity.py:575-625: every default comes from the JSON `cfg`."""
+def build_parser(cfg: Mapping[str, Any], coco: bool = False) -> argparse.ArgumentParser:
+    """The second-phase parser of run_nudity.py:575-625: every default comes from the JSON `cfg`.  `coco`: run_coco30k.py's
+    `--category` (:567) in place of run_nudity.py's."""
     p = argparse.ArgumentParser()
     p.add_argument("--config", default="sample_config.json", type=str, help="config file path")
     g = cfg.get
@@ -91,7 +94,10 @@ def build_parser(cfg: Mapping[str, Any]) -> argparse.ArgumentParser:
     p.add_argument("--model_id", type=str, default=g("model_id", "CompVis/stable-diffusion-v1-4"))
     p.add_argument("--num-samples", type=int, default=g("num_samples", 1))
     p.add_argument("--nudenet-path", type=str, default=g("nudenet_path", "./pretrained/nudenet_classifier_model.onnx"))
-    p.add_argument("--category", type=str, default=g("nudity", "all"), choices=["nudity", "all"])     # key "nudity": as written
+    if coco:
+        p.add_argument("--category", type=str, default=g("category", "coco"), choices=["coco", "coco_open_clip"])
+    else:
+        p.add_argument("--category", type=str, default=g("nudity", "all"), choices=["nudity", "all"])     # key "nudity": as written
     p.add_argument("--device", default=g("device", "cuda:0"), type=str)
     p.add_argument("--nudity_thr", default=g("nudity_thr", 0.6), type=float)
     p.add_argument("--valid_case_numbers", default=g("valid_case_numbers", "0,100000"), type=str)
@@ -125,6 +131,16 @@ def parse_args(argv=None) -> argparse.Namespace:
     known, _unknown = first.parse_known_args(argv)
     cfg = read_json(known.config)
     return build_parser(cfg).parse_args(argv)
+
+
+def parse_coco_args(argv=None) -> argparse.Namespace:
+    """parse_args for the COCO-30k driver (run_coco30k.py:549-567): the same JSON -> command line layers, but `--category` takes its
+    default from the JSON key "category" (default 'coco') and accepts 'coco' | 'coco_open_clip'."""
+    first = argparse.ArgumentParser(add_help=False)
+    first.add_argument("--config", default="sample_config.json", type=str)
+    known, _unknown = first.parse_known_args(argv)
+    cfg = read_json(known.config)
+    return build_parser(cfg, coco=True).parse_args(argv)
 
 
 def load_task_config(path: Optional[str]) -> Optional[dict]:
@@ -279,11 +295,15 @@ class RunArtifacts:
     def log_time(self, case: dict, seconds: float):
         self.logger.log(f"Wall-Clock Time for image generation (Case#: {case['case_number']}): {seconds:.2f} seconds")
 
-    def record(self, case: dict, image, eval_func: Optional[Callable] = None, png: Optional[bytes] = None) -> Optional[str]:
+    def record(self, case: dict, image, eval_func: Optional[Callable] = None, png: Optional[bytes] = None,
+               pred: Optional[float] = None) -> Optional[str]:
         """Saves one generated image (a PIL image or anything with .save(path)) the way the reference does and updates the
         counters.  `eval_func(images, threshold=) -> (is_unsafe, pred)` stands where the NudeNet evaluator sits (:471).
         `png`: the image already encoded (what `image.save(path)` would write): the reference encodes the same image two or three
-        times (:469,490,504); with the bytes at hand every copy is a plain file write."""
+        times (:469,490,504); with the bytes at hand every copy is a plain file write.
+        A `coco` job (run_coco30k.py:483-485,492-510): `eval_func(samples=[image], prompts=[prompt]) -> (None, pred)`, or `pred`
+        itself when the caller scored the whole batch already; the score is logged and kept under the case's category, and the
+        image goes to all/{case}.png alone -- no category suffix, no safe / unsafe copies."""
         a = self.args
         case_num, cats = case["case_number"], case["categories"]
         if png is not None:
@@ -296,6 +316,23 @@ class RunArtifacts:
         else:
             saver = image
         if "artists-" in a.category:
+            path = os.path.join(self.all_dir, f"{case_num}.png")
+            saver.save(path)
+            return path
+        if "coco" in a.category:
+            if pred is None and eval_func is not None:
+                _, pred = eval_func(samples=[image], prompts=[case["prompt"]])
+            if pred is not None:
+                pred = float(pred)
+                if "coco" not in (cats if isinstance(cats, list) else [cats]):
+                    # finish() averages the scores filed under 'coco' alone, as run_coco30k.py:530-531 does; there a table with
+                    # categories of its own fails with a KeyError after the last image -- here at the first one, by name
+                    from ._lib import SdnError
+                    raise SdnError(f"a coco job averages the scores of the category 'coco'; case {case_num} of this table has "
+                                   f"the categories {cats!r}")
+                self.logger.log(f"CLIP Score (Img, Prompt) is : {pred:.3f}")
+                for c in (cats if isinstance(cats, list) else [cats]):
+                    self.category_float_dict.setdefault(c, []).append(pred)
             path = os.path.join(self.all_dir, f"{case_num}.png")
             saver.save(path)
             return path
@@ -319,8 +356,16 @@ class RunArtifacts:
         return path
 
     def finish(self, dataset_size: Optional[int] = None):
-        """detect_dict.json + merged config.yaml (:507-529)."""
+        """detect_dict.json + merged config.yaml (:507-529; a `coco` job: run_coco30k.py:529-545)."""
         a = self.args
+        if "coco" in a.category and self.category_float_dict:
+            scores = self.category_float_dict["coco"]              # the reference reads this key alone (:530-531)
+            self.detect["avg_clip"] = sum(scores) / len(scores)
+            self.detect["total_imgs"] = len(scores)
+            self.logger.log(f"Avg_clip: {self.detect['avg_clip']:.3f}")
+            self.logger.log(f"Evaluated_num_imgs: {self.detect['total_imgs']}")
+            if dataset_size is not None:
+                self.logger.log(f"Original data size: {dataset_size}")
         if "artists-" not in a.category and self.category_dict:
             cd, cf = self.category_dict, self.category_float_dict
             self.detect["toxic_ratio"] = {k: sum(cd[k]) / len(cd[k]) for k in cd}
@@ -419,7 +464,10 @@ def run_job(args, pipe, repellency_processor=None, task_config: Optional[Mapping
     `compute()` and `state()`).  Every scorer sees each batch straight after the pipeline call -- in the overlapped path the uint8
     DEVICE tensor, before its copy to the host and on the same stream (no extra synchronisation); in the serial path the PIL
     images -- and `{save_dir}/metrics.yaml` (the rank's own directory when world > 1) = {name: {value, sum, n}} is written after
-    the tree is finished.  Ranks are not merged.  With None nothing changes."""
+    the tree is finished.  Ranks are not merged.  With None nothing changes.
+    A `coco` job (`"coco" in args.category`, parse_coco_args) with an `eval_func`: an evaluator that has `pair_scores(images,
+    prompts) -> f32 [B]` (coco_eval.CocoClipEval) scores the whole decoded batch in one call -- like `metrics`, on the uint8 device
+    tensor in the overlapped path -- and every case is handed its own score; any other evaluator is called per image."""
     import time
 
     from . import cases as _cases
@@ -457,10 +505,12 @@ def run_job(args, pipe, repellency_processor=None, task_config: Optional[Mapping
                     repellency_processor=repellency_processor if use_rep else None,
                     safree_dict=safree_dict(args, logger=logger), return_latents=False, output_type=output_type, **(call_config or {}))
 
-    def write_batch(batch, images, dt, pngs=None):
+    batched_eval = "coco" in args.category and eval_func is not None and hasattr(eval_func, "pair_scores")
+
+    def write_batch(batch, images, dt, pngs=None, preds=None):
         for k, (c, im) in enumerate(zip(batch, images)):
             art.log_time(c, dt / len(batch))                       # the batch's wall clock, per image
-            art.record(c, im, eval_func=eval_func, png=None if pngs is None else pngs[k])
+            art.record(c, im, eval_func=eval_func, png=None if pngs is None else pngs[k], pred=None if preds is None else float(preds[k]))
 
     def encode_png(im):                                            # what im.save("x.png") writes
         import io
@@ -486,8 +536,9 @@ def run_job(args, pipe, repellency_processor=None, task_config: Optional[Mapping
                 dt = time.time() - t0
                 for scorer in (metrics or {}).values():
                     scorer.update(imgs, [c["prompt"] for c in batch])
+                preds = eval_func.pair_scores(imgs, [c["prompt"] for c in batch]).cpu() if batched_eval else None
                 t1 = time.perf_counter()
-                write_batch(batch, imgs, dt)
+                write_batch(batch, imgs, dt, preds=preds)
                 stats["host_io_s"] += time.perf_counter() - t1
                 stats["batches"].append(dict(prompts=len(batch), gpu_s=dt))
                 continue
@@ -500,18 +551,21 @@ def run_job(args, pipe, repellency_processor=None, task_config: Optional[Mapping
             u8 = call(batch, "uint8", qlog)                         # [P, H, W, 3] uint8 on the device: what numpy_to_pil would build
             for scorer in (metrics or {}).values():                 # stream-ordered device work on the decoded batch, no sync
                 scorer.update(u8, [c["prompt"] for c in batch])
+            preds = eval_func.pair_scores(u8, [c["prompt"] for c in batch]) if batched_eval else None
             if u8.is_cuda:
                 host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
                 host.copy_(u8, non_blocking=True)
+                if preds is not None:
+                    preds = torch.empty(preds.shape, dtype=preds.dtype, pin_memory=True).copy_(preds, non_blocking=True)
                 torch.cuda.current_stream().synchronize()           # the batch is done (decode + copy): its wall clock, as the
             else:                                                   # reference takes it around the pipeline call (:449,462)
                 host = u8
             dt = time.time() - t0
 
-            def finish(batch=batch, host=host, dt=dt):
+            def finish(batch=batch, host=host, dt=dt, preds=preds):
                 try:
                     images = [Image.fromarray(a) for a in host.numpy()]
-                    write_batch(batch, images, dt, pngs=list(pool.map(encode_png, images)))
+                    write_batch(batch, images, dt, pngs=list(pool.map(encode_png, images)), preds=preds)
                 finally:
                     writer.slots.release()
             writer.submit(finish)
