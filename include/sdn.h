@@ -647,7 +647,7 @@ int sdn_gaussian_sample(const float* moments, const float* noise, int32_t batch,
 int sdn_image_postprocess(const float* image_nchw, int32_t batch, int32_t channels, int32_t height, int32_t width,
                           float* out_nhwc01, uint8_t* out_nhwc_u8, void* stream);
 /* building blocks of the decoder's single-head d = 512 attention (also usable alone):
- * out[b, co, p] = bias[co] + sum_ci w[co, ci] * in_scale * z[b, ci, p]   (1x1 conv on an fp32 NCHW map, C <= 16) */
+ * out[b, co, p] = bias[co] + sum_ci w[co, ci] * in_scale * z[b, ci, p]   (1x1 conv on an fp32 NCHW map, C <= 32) */
 int sdn_latent_mix(const float* z, const float* w, const float* bias, int32_t batch, int32_t channels, int32_t hw,
                    float in_scale, float* out, void* stream);
 /* out[r, :] = softmax(scale * scores[r, :n]) as 16-bit (dtype 0 bf16 / 1 fp16) or f32 (dtype 2); n % 4 == 0, n <= 16384, ld_* % 4

@@ -8,6 +8,9 @@ The reference enters through `DDPMScheduler.from_pretrained(model_id, subfolder=
     text_encoder/config.json     text_encoder/model.safetensors | pytorch_model.bin
     tokenizer/{vocab.json,merges.txt,...}      (handed to transformers.CLIPTokenizer when the files are there)
     scheduler/scheduler_config.json
+and, for the SD-v3 family (run_nudity_sdv3.py:64-72; SD3SafeDenoiserPipeline.from_pretrained):
+    transformer/config.json      transformer/diffusion_pytorch_model.* (or shards + *.safetensors.index.json)
+    text_encoder{,_2,_3}/        tokenizer{,_2,_3}/
 Host logic only (files -> dicts); the engine classes upload the tensors.  Configuration values the engine's plans do not
 implement are rejected loudly instead of being ignored.
 """
@@ -110,6 +113,25 @@ def unet_kwargs(cfg: dict) -> dict:
     return out
 
 
+def mmdit_kwargs(cfg: dict) -> dict:
+    """SD3Transformer2DModel(**kwargs) from transformer/config.json (the SD-v3 family; SD3-medium's file).  The plan has no q/k
+    RMS norm and no second attention per block (the SD-3.5 additions), and its text projection is as wide as the blocks."""
+    _require(cfg, "transformer", qk_norm=None)
+    if cfg.get("dual_attention_layers"):
+        raise NotImplementedError(f"transformer: config value dual_attention_layers = {cfg['dual_attention_layers']!r} is not "
+                                  "implemented by the engine's plan (needs ())")
+    arch = cfg.get("_class_name")
+    if arch is not None and arch != "SD3Transformer2DModel":
+        raise NotImplementedError(f"transformer: _class_name = {arch!r} is not implemented (needs 'SD3Transformer2DModel')")
+    heads, hd = cfg.get("num_attention_heads", 24), cfg.get("attention_head_dim", 64)
+    if "caption_projection_dim" in cfg and cfg["caption_projection_dim"] != heads * hd:
+        raise NotImplementedError(f"transformer: config value caption_projection_dim = {cfg['caption_projection_dim']!r} is not "
+                                  f"implemented by the engine's plan (needs num_attention_heads * attention_head_dim = {heads * hd})")
+    keys = ("in_channels", "out_channels", "sample_size", "patch_size", "num_layers", "num_attention_heads", "attention_head_dim",
+            "joint_attention_dim", "pooled_projection_dim", "pos_embed_max_size")
+    return {k: cfg[k] for k in keys if k in cfg}
+
+
 def vae_kwargs(cfg: dict) -> dict:
     _require(cfg, "vae", act_fn="silu")
     keys = ("in_channels", "out_channels", "latent_channels", "block_out_channels", "layers_per_block", "norm_num_groups",
@@ -203,10 +225,15 @@ def t5_kwargs(cfg: dict) -> dict:
     return {k: cfg[k] for k in keys if k in cfg}
 
 
-def load_tokenizer(model_dir: str):
-    """transformers.CLIPTokenizer from `tokenizer/` when its vocabulary files exist; None otherwise (pass tokenizer=...)."""
-    d = os.path.join(model_dir, "tokenizer")
-    if not (os.path.isfile(os.path.join(d, "vocab.json")) and os.path.isfile(os.path.join(d, "merges.txt"))):
-        return None
-    from transformers import CLIPTokenizer
-    return CLIPTokenizer.from_pretrained(d)
+def load_tokenizer(model_dir: str, subfolder: str = "tokenizer"):
+    """transformers.CLIPTokenizer from `tokenizer/` (SD-v3: also `tokenizer_2/`) when its vocabulary files exist, or
+    transformers.T5TokenizerFast from a folder that holds a sentencepiece model instead (SD-v3's `tokenizer_3/`); None otherwise
+    (pass tokenizer=...)."""
+    d = os.path.join(model_dir, subfolder)
+    if os.path.isfile(os.path.join(d, "vocab.json")) and os.path.isfile(os.path.join(d, "merges.txt")):
+        from transformers import CLIPTokenizer
+        return CLIPTokenizer.from_pretrained(d)
+    if os.path.isfile(os.path.join(d, "spiece.model")):
+        from transformers import T5TokenizerFast
+        return T5TokenizerFast.from_pretrained(d)
+    return None

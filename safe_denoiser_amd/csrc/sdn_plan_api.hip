@@ -93,7 +93,7 @@ int sdn_vae_encoder_create(const sdn_vae_config* cfg, sdn_unet** out) {
   sdn_unet* u = nullptr;
   const int rc = sdn_vae_decoder_create(cfg, &u);              // same config checks; the plan is rebuilt as an encoder
   if (rc != SDN_OK) return rc;
-  if (2 * cfg->latent_channels > 16) { delete u; return SDN_E_INVALID; }
+  if (2 * cfg->latent_channels > 32) { delete u; return SDN_E_INVALID; }   // quant_conv mixes the 2L moments (sdn_latent_mix: C <= 32)
   u->kind = VAE_ENCODER;
   u->plans.clear(); u->params.clear(); u->param_index.clear(); u->weight_bytes = 0;
   get_plan(u, 1);

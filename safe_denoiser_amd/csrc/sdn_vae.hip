@@ -1,7 +1,7 @@
 // Small kernels around the VAE decoder plan (the convolutions, GroupNorms and linears of
 // the decoder run on the GEMM / norm kernels of the UNet):
 //   k_latent_mix    post_quant_conv: a 1x1 conv on the fp32 NCHW latent (C <= 16), with the 1/scaling_factor of
-//                   StableDiffusionPipeline.decode_latents folded in;
+//                   StableDiffusionPipeline.decode_latents folded in; and the encoders' quant_conv on 2L moments (C <= 32);
 //   k_softmax_rows  softmax(scale * S) over fp32 rows -> 16-bit P (the decoder's single-head, d = 512 mid-block
 //                   attention is run as Q K^T GEMM -> row softmax -> P V GEMM: its head dim does not fit the flash
 //                   kernel's register tile, and it is 1.5 % of the decoder's FLOPs);
@@ -16,13 +16,16 @@ namespace {
 
 constexpr int THREADS = 256;
 
+// MAXC = 16: the decoders' post_quant_conv and the 4-channel encoder's quant_conv, as ever; MAXC = 32: quant_conv on the 2 x 16
+// moments of SD-v3's 16-channel encoder.  C <= MAXC is the host's check.
+template <int MAXC>
 __global__ void __launch_bounds__(THREADS)
 k_latent_mix(const float* __restrict__ z, const float* __restrict__ w, const float* __restrict__ bias, int B, int C,
              int hw, float in_scale, float* __restrict__ out) {
   const long total = (long)B * hw;
   for (long e = (long)blockIdx.x * THREADS + threadIdx.x; e < total; e += (long)gridDim.x * THREADS) {
     const long b = e / hw, p = e - b * hw;
-    float v[16];
+    float v[MAXC];
     for (int ci = 0; ci < C; ++ci) v[ci] = z[(b * C + ci) * hw + p] * in_scale;
     for (int co = 0; co < C; ++co) {
       float acc = bias[co];
@@ -222,10 +225,14 @@ inline unsigned grid_for(long total) {
 
 extern "C" int sdn_latent_mix(const float* z, const float* w, const float* bias, int32_t batch, int32_t channels,
                               int32_t hw, float in_scale, float* out, void* stream) {
-  if (!z || !w || !bias || !out || batch < 0 || channels <= 0 || channels > 16 || hw <= 0) return SDN_E_INVALID;
+  if (!z || !w || !bias || !out || batch < 0 || channels <= 0 || channels > 32 || hw <= 0) return SDN_E_INVALID;
   if (batch == 0) return SDN_OK;
-  hipLaunchKernelGGL(k_latent_mix, dim3(grid_for((long)batch * hw)), dim3(THREADS), 0, (hipStream_t)stream, z, w, bias,
-                     batch, channels, hw, in_scale, out);
+  if (channels <= 16)
+    hipLaunchKernelGGL(k_latent_mix<16>, dim3(grid_for((long)batch * hw)), dim3(THREADS), 0, (hipStream_t)stream, z, w, bias,
+                       batch, channels, hw, in_scale, out);
+  else
+    hipLaunchKernelGGL(k_latent_mix<32>, dim3(grid_for((long)batch * hw)), dim3(THREADS), 0, (hipStream_t)stream, z, w, bias,
+                       batch, channels, hw, in_scale, out);
   return sdn_launch_status();
 }
 

@@ -47,6 +47,11 @@ ERASE_IDS = {
     "safree_neg_prompt_rep_threshold_time": ("safree", "threshold_time", True),
 }
 
+# SD-v3: erase_id -> (SAFREE text projection, class has a repellency block) (SD_FUNCTIONS, run_nudity_sdv3.py:34-39 and
+# run_coco30k_sdv3.py:41-46: StableDiffusion3Pipeline, SafreeDiffusion3Pipeline, SaferDiffusion3Pipeline).  One engine class runs all
+# three: `safree=` switches the projection, and only the last id hands the processor over.
+SD3_ERASE_IDS = {"std": (False, False), "safree_neg_prompt": (True, False), "safree_neg_prompt_rep_time": (True, True)}
+
 # ModifiedSLDPipeline.__call__'s own defaults (models/textuals/modified_sld_pipeline.py:304-308): what an SLD-family class runs
 # with when the driver splats no SafetyConfig -- i.e. for 'rece', whose id does not contain "sld" (run_nudity.py:329-334)
 SLD_CALL_DEFAULTS = dict(sld_guidance_scale=1000, sld_warmup_steps=10, sld_threshold=0.01, sld_momentum_scale=0.3,
@@ -82,9 +87,10 @@ def load_yaml(file_path: str) -> dict:
         return yaml.load(f, Loader=yaml.FullLoader)
 
 
-def build_parser(cfg: Mapping[str, Any], coco: bool = False) -> argparse.ArgumentParser:
+def build_parser(cfg: Mapping[str, Any], coco: bool = False, sd3: bool = False) -> argparse.ArgumentParser:
     """The second-phase parser of run_nudity.py:575-625: every default comes from the JSON `cfg`.  `coco`: run_coco30k.py's
-    `--category` (:567) in place of run_nudity.py's."""
+    `--category` (:567) in place of run_nudity.py's.  `sd3`: the SD-v3 drivers' parsers (run_nudity_sdv3.py:475-524,
+    run_coco30k_sdv3.py:462-486), which differ in one default: `--guidance_scale` 3.5."""
     p = argparse.ArgumentParser()
     p.add_argument("--config", default="sample_config.json", type=str, help="config file path")
     g = cfg.get
@@ -105,7 +111,7 @@ def build_parser(cfg: Mapping[str, Any], coco: bool = False) -> argparse.Argumen
     for name, typ, dflt in (("prompt_len", int, 16), ("every_k", int, 3), ("max_length", int, 77), ("iter", int, 3000),
                             ("eval_step", int, 50), ("seed", int, None), ("lr", float, 0.1), ("weight_decay", float, 0.1),
                             ("prompt_bs", int, 1), ("loss_weight", float, 1.0), ("print_step", int, 100),
-                            ("batch_size", int, 1), ("image_length", int, 512), ("guidance_scale", float, 7.5),
+                            ("batch_size", int, 1), ("image_length", int, 512), ("guidance_scale", float, 3.5 if sd3 else 7.5),
                             ("num_inference_steps", int, 50), ("num_images_per_prompt", int, 1),
                             ("q16_path", str, "./pretrained/Q16_prompts.p"), ("clip_model", str, "ViT-H-14"),
                             ("clip_pretrain", str, "laion2b_s32b_b79k"), ("target_prompts", str, None),
@@ -124,23 +130,34 @@ def build_parser(cfg: Mapping[str, Any], coco: bool = False) -> argparse.Argumen
     return p
 
 
-def parse_args(argv=None) -> argparse.Namespace:
-    """Two-phase parse (run_nudity.py:534-625): `--config` first, then every flag with the JSON as its defaults."""
+def _two_phase(argv, **flavour) -> argparse.Namespace:
     first = argparse.ArgumentParser(add_help=False)
     first.add_argument("--config", default="sample_config.json", type=str)
     known, _unknown = first.parse_known_args(argv)
     cfg = read_json(known.config)
-    return build_parser(cfg).parse_args(argv)
+    return build_parser(cfg, **flavour).parse_args(argv)
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    """Two-phase parse (run_nudity.py:534-625): `--config` first, then every flag with the JSON as its defaults."""
+    return _two_phase(argv)
 
 
 def parse_coco_args(argv=None) -> argparse.Namespace:
     """parse_args for the COCO-30k driver (run_coco30k.py:549-567): the same JSON -> command line layers, but `--category` takes its
     default from the JSON key "category" (default 'coco') and accepts 'coco' | 'coco_open_clip'."""
-    first = argparse.ArgumentParser(add_help=False)
-    first.add_argument("--config", default="sample_config.json", type=str)
-    known, _unknown = first.parse_known_args(argv)
-    cfg = read_json(known.config)
-    return build_parser(cfg, coco=True).parse_args(argv)
+    return _two_phase(argv, coco=True)
+
+
+def parse_sd3_args(argv=None) -> argparse.Namespace:
+    """parse_args for the SD-v3 nudity driver (run_nudity_sdv3.py:433-525): the same two phases; `--guidance_scale` defaults to 3.5
+    and `--category` takes its default from the JSON key "nudity" (default 'all'), as there (:481,501)."""
+    return _two_phase(argv, sd3=True)
+
+
+def parse_sd3_coco_args(argv=None) -> argparse.Namespace:
+    """parse_coco_args for the SD-v3 COCO-30k driver (run_coco30k_sdv3.py:462-486): `--guidance_scale` defaults to 3.5."""
+    return _two_phase(argv, coco=True, sd3=True)
 
 
 def load_task_config(path: Optional[str]) -> Optional[dict]:
@@ -156,6 +173,9 @@ def repellency_kwargs(task_config: Mapping[str, Any], num_inference_steps: int, 
     """Arguments of get_repellency_method built from the YAML as run_nudity.py:309-325 builds them (ref_data / embed_fn /
     forward_fn are the caller's: they need the model).  `repellency.guidance_scale` is NOT forwarded (ignored there too)."""
     rc = task_config["repellency"]
+    if not hasattr(scheduler, "betas"):            # a flow-matching scheduler has no beta table: the SD-v3 driver passes None (run_nudity_sdv3.py:252-262)
+        return dict(name=rc["method"], num_timesteps=num_inference_steps, max_idx=None, beta_min=None, beta_max=None,
+                    n_embed=rc["n_embed"], scheduler=scheduler, **rc["params"])
     return dict(name=rc["method"], num_timesteps=num_inference_steps, max_idx=len(scheduler.betas),
                 beta_min=scheduler.beta_start, beta_max=scheduler.beta_end, n_embed=rc["n_embed"], scheduler=scheduler,
                 **rc["params"])
@@ -168,19 +188,25 @@ def build_repellency(args, pipe, task_config: Mapping[str, Any], get_repellency_
     the result is run_job's `repellency_processor`.  `pipe` needs `.vae` (with encoder weights) and `.scheduler`.
     The images are a lazy set by default -- `project` embeds `n_embed` at a time and the [M, 3, 512, 512] stack is never resident;
     `eager=True` builds the tensor the reference builds (same proj_ref bits under the same global seed).
-    `get_repellency_method`: the registry function of the front-end to use (default repellency_methods_threshold's; the CoPro /
-    SD-v3 callers pass repellency_methods_fast's / repellency_methods_fast_sdv3's).
+    `get_repellency_method`: the registry function of the front-end to use (default repellency_methods_threshold's; the CoPro
+    callers pass repellency_methods_fast's).  An SD-v3 pipeline (`pipe.family == "sd3"`) takes the SD-v3 driver's block
+    (run_nudity_sdv3.py:233-262): the default registry is repellency_methods_fast_sdv3's, `forward_fn` is None, and the embed_fn
+    is the same `sample() * scaling_factor` -- without the VAE's shift, as there (:246-249).
     With W > 1 ranks (default: the initialised process group) only rank 0 reads images and writes the cache file; the others
     receive proj_ref through dist.broadcast_proj_ref and build their processor around it."""
     from . import data as _data, dist as _dist
     _ = task_config["mean_processor"]                           # required and unused (:297)
+    sd3 = getattr(pipe, "family", None) == "sd3"
     if get_repellency_method is None:
-        from .repellency.repellency_methods_threshold import get_repellency_method
+        if sd3:
+            from .repellency.repellency_methods_fast_sdv3 import get_repellency_method
+        else:
+            from .repellency.repellency_methods_threshold import get_repellency_method
     if rank is None or world is None:
         import torch.distributed as td
         rank, world = (td.get_rank(), td.get_world_size()) if td.is_initialized() else (0, 1)
     kw = repellency_kwargs(task_config, args.num_inference_steps, pipe.scheduler)
-    common = dict(embed_fn=pipe.vae.embed_fn(), forward_fn=pipe.scheduler.add_noise)
+    common = dict(embed_fn=pipe.vae.embed_fn(), forward_fn=None if sd3 else pipe.scheduler.add_noise)
     proc = None
     if rank == 0:
         data_config = dict(task_config["data"])
@@ -454,7 +480,15 @@ def run_job(args, pipe, repellency_processor=None, task_config: Optional[Mapping
     table (`args.data`, `--valid_case_numbers`), shard it over the ranks, and for every batch of prompts (each with its own
     guidance scale and seed) call `pipe(prompt, ..., negative_prompt, negative_prompt_space, generator, repellency_processor, safree_dict,
     **SLD config)` once, then save / classify / log every image exactly as the reference does per prompt.
-    `pipe`: a SafeDenoiserPipeline with text_encoder, tokenizer and vae attached.
+    `pipe`: a SafeDenoiserPipeline with text_encoder, tokenizer and vae attached -- or an SD3SafeDenoiserPipeline (`pipe.family ==
+    "sd3"`) with text_front_end and vae attached: then `args.erase_id` is one of SD3_ERASE_IDS and the call is the SD-v3 driver's
+    (run_nudity_sdv3.py:351-360, run_coco30k_sdv3.py): `pipe(prompts, negative_prompt="", num_inference_steps, guidance_scale=[one per
+    case], generator=[one per case], height, width, repellency_processor, safree=)`; everything after the call is shared.
+    ONE DIFFERENCE from the SD-v3 reference: it calls its pipeline once per prompt and draws the re-noise of every window step from
+    the unseeded GLOBAL generator (`randn_like`); the batched loop draws P tensors per window step from that same generator.  With
+    `prompts_per_batch=1` the order of draws is the reference's; with larger batches the prompts receive other draws of the same
+    stream (prompt p of a batch takes draw p of each window step, not a run of consecutive steps).  The per-prompt generators seed
+    the initial latents only, as in the reference.
     `overlap_io` (default: on when the pipeline can hand back uint8 device tensors): the images of batch k are copied to pinned
     host memory asynchronously and written / classified / logged by a worker thread while the GPU runs batch k + 1 (the reference
     is serial: per image two or three PNG encodes + the classifier sit between two pipeline calls, :462-504); the output files
@@ -471,7 +505,14 @@ def run_job(args, pipe, repellency_processor=None, task_config: Optional[Mapping
     import time
 
     from . import cases as _cases
-    family, variant, has_rep_block = ERASE_IDS[args.erase_id]
+    sd3 = getattr(pipe, "family", None) == "sd3"
+    if sd3:
+        if args.erase_id not in SD3_ERASE_IDS:
+            raise KeyError(f"erase_id {args.erase_id!r} is not one of the SD-v3 drivers' {sorted(SD3_ERASE_IDS)}")
+        use_safree, has_rep_block = SD3_ERASE_IDS[args.erase_id]
+        family = variant = None
+    else:
+        family, variant, has_rep_block = ERASE_IDS[args.erase_id]
     # SD_FUNCTIONS[erase_id] fixes the pipeline class, hence the gating window (run_nudity.py:56-73,277-279): a pipe built for
     # another variant would silently run a different window than the reference does for this erase_id
     if variant is not None and getattr(pipe, "variant", variant) != variant:
@@ -483,7 +524,8 @@ def run_job(args, pipe, repellency_processor=None, task_config: Optional[Mapping
     # only the *_Rep classes run the repellency block (ERASE_IDS above); everywhere else the processor is built and ignored
     use_rep = args.task_config is not None and has_rep_block
     space, neg = negative_prompts(args)
-    safe_config = SLD_CONFIGS[args.safe_level] if "sld" in args.erase_id else None      # keyed on the id's TEXT, as there (:329)
+    # keyed on the id's TEXT, as there (:329); the SD-v3 drivers have no SLD class and set `safe_config = None` (run_nudity_sdv3.py:269)
+    safe_config = SLD_CONFIGS[args.safe_level] if ("sld" in args.erase_id and not sd3) else None
     if safe_config is not None:
         log.log(f"SLD safe level: {args.safe_level}")
         log.log(f"SLD safe config: {safe_config}")
@@ -499,6 +541,13 @@ def run_job(args, pipe, repellency_processor=None, task_config: Optional[Mapping
     stats = dict(batches=[], host_io_s=0.0)
 
     def call(batch, output_type, logger):
+        if sd3:                                                    # run_nudity_sdv3.py:351-360, P prompts at once
+            out = pipe([c["prompt"] for c in batch], negative_prompt="", num_inference_steps=args.num_inference_steps,
+                       guidance_scale=[c["guidance"] for c in batch], generator=_cases.generators(batch, device=device),
+                       height=args.image_length, width=args.image_length,
+                       repellency_processor=repellency_processor if use_rep else None, safree=use_safree, return_latents=False,
+                       output_type=output_type)
+            return out.images
         return pipe([c["prompt"] for c in batch], num_inference_steps=args.num_inference_steps, guidance_scale=[c["guidance"] for c in batch],
                     negative_prompt=neg, negative_prompt_space=space, height=args.image_length, width=args.image_length,
                     generator=_cases.generators(batch, device=device),

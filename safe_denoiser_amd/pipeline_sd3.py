@@ -56,6 +56,8 @@ SD3_NEGATIVE_PROMPT_SPACE = ["Sexual Acts", "Content Meant to Arouse Sexual Exci
 
 
 class SD3SafeDenoiserPipeline:
+    family = "sd3"              # what driver.run_job / build_repellency select the SD-v3 call and registry by
+
     def __init__(self, transformer, scheduler, vae=None, text_front_end=None, transformer_hi=None, precision_schedule=None):
         self.transformer, self.scheduler, self.vae = transformer, scheduler, vae
         # Precision schedule, as SafeDenoiserPipeline's `unet_hi` / `precision_schedule`: `transformer_hi` is a second plan over the
@@ -75,6 +77,67 @@ class SD3SafeDenoiserPipeline:
         self._rng = {}
         self.batched_rng = True     # False: one torch.randn per prompt, as the reference's Python loop would draw
 
+    @classmethod
+    def from_pretrained(cls, model_dir: str, *, tokenizer=None, tokenizer_2=None, tokenizer_3=None, torch_dtype=torch.float16,
+                        image_length: int = 512, precision: Optional[str] = None, vae_precision: Optional[str] = None,
+                        weights_variant: Optional[str] = None, device="cuda", scheduler=None, **ignored):
+        """`pipeline_func.from_pretrained(args.model_id, torch_dtype=torch.float16)` (run_nudity_sdv3.py:64-72) for a LOCAL
+        diffusers-layout directory: `transformer/` (one file or shards with an index) -> the MMDiT plan for `image_length` x
+        `image_length` images (the plan's latent side is image_length // 8, whatever `sample_size` the file names), `vae/` -> the
+        16-channel AutoencoderKL, `scheduler/scheduler_config.json` unless a scheduler object is passed, and the three text encoders
+        on the engine (SD3TextFrontEnd.from_pretrained) when there are three tokenizers: the caller's, else what
+        checkpoint.load_tokenizer finds in `tokenizer/`, `tokenizer_2/`, `tokenizer_3/`; with none, `text_front_end` is None and the
+        call takes embeddings.
+        `precision`: None = a 16-bit plan of `torch_dtype`; "fp32" / "bf16x3" = the MMDiT's fp32-storage plans; "scheduled" = the
+        fp16 plan plus `transformer_hi`, the bf16x3 plan over the same state dict, on the steps of the repellency window
+        (`precision_schedule={"window": True}`), as SafeDenoiserPipeline.from_pretrained.  `vae_precision`: AutoencoderKL's.  The
+        VAE and the text encoders take the 16-bit type in every mode.  Hub arguments (`revision`, ...) are accepted and ignored."""
+        import os
+
+        from . import checkpoint as ck
+        from .mmdit import SD3Transformer2DModel
+        from .schedulers import FlowMatchEulerDiscreteScheduler
+        from .text_sd3 import CLIP_SEQUENCE_LENGTH, MAX_SEQUENCE_LENGTH, SD3TextFrontEnd
+        from .vae import AutoencoderKL
+        if not os.path.isdir(model_dir):
+            raise FileNotFoundError(f"{model_dir}: not a local directory (there is no hub access; pass a diffusers-layout checkpoint directory)")
+        if scheduler is None:
+            scheduler = FlowMatchEulerDiscreteScheduler.from_pretrained(model_dir, subfolder="scheduler")
+        dt16 = torch_dtype if torch_dtype in (torch.bfloat16, torch.float16) else torch.float16
+        tdir = os.path.join(model_dir, "transformer")
+        tcfg = dict(ck.mmdit_kwargs(ck.read_config(tdir)), sample_size=image_length // 8)
+        tsd = ck.load_weights(tdir, weights_variant)
+        text_len = CLIP_SEQUENCE_LENGTH + MAX_SEQUENCE_LENGTH
+        hi = schedule = None
+        if precision == "scheduled":
+            schedule = ignored.pop("precision_schedule", None) or {"window": True}
+            tr = SD3Transformer2DModel(text_len=text_len, dtype=torch.float16, **tcfg)
+            hi = SD3Transformer2DModel(text_len=text_len, precision="bf16x3", **tcfg)
+            hi.load_state_dict(tsd, device=device)
+        elif precision is not None:
+            tr = SD3Transformer2DModel(text_len=text_len, precision=precision, **tcfg)
+        else:
+            tr = SD3Transformer2DModel(text_len=text_len, dtype=torch_dtype, **tcfg)
+        tr.load_state_dict(tsd, device=device)
+        del tsd
+        vae = None
+        if os.path.isdir(os.path.join(model_dir, "vae")):
+            vcfg = ck.vae_kwargs(ck.read_config(os.path.join(model_dir, "vae")))
+            # the decoder plan is built for this run's latents, as the MMDiT plan is: latent side x 2 per level above the first
+            vcfg["sample_size"] = (image_length // 8) * 2 ** (len(vcfg.get("block_out_channels", (0,) * 4)) - 1)
+            vae = AutoencoderKL(dtype=dt16, precision=vae_precision, **vcfg)
+            vae.load_state_dict(ck.load_weights(os.path.join(model_dir, "vae"), weights_variant), device=device)
+        toks = [tok if tok is not None else ck.load_tokenizer(model_dir, sub)
+                for tok, sub in ((tokenizer, "tokenizer"), (tokenizer_2, "tokenizer_2"), (tokenizer_3, "tokenizer_3"))]
+        fe = None
+        if all(t is not None for t in toks):
+            fe = SD3TextFrontEnd.from_pretrained(model_dir, tokenizer=toks[0], tokenizer_2=toks[1], tokenizer_3=toks[2], dtype=dt16)
+        return cls(tr, scheduler, vae=vae, text_front_end=fe, transformer_hi=hi, precision_schedule=schedule)
+
+    def to(self, *args, **kwargs):
+        """`pipe.to(device)` of the reference's load_sd: the engine's weights already live on the GPU."""
+        return self
+
     @torch.no_grad()
     def __call__(self, prompt=None, height: Optional[int] = None, width: Optional[int] = None,
                  num_inference_steps: int = 50, guidance_scale: float = 7.0, generator=None, latents=None,
@@ -83,7 +146,12 @@ class SD3SafeDenoiserPipeline:
                  noise_fn: Optional[Callable] = None, rescaled_text_embeddings: Optional[torch.Tensor] = None,
                  masked_embs=None, negspace_embs: Optional[torch.Tensor] = None, safree_alpha: float = 0.01,
                  negative_prompt=None, negative_prompt_embeds: Optional[torch.Tensor] = None,
-                 negative_pooled_prompt_embeds: Optional[torch.Tensor] = None, **kwargs):
+                 negative_pooled_prompt_embeds: Optional[torch.Tensor] = None, safree: bool = True, **kwargs):
+        """`guidance_scale`: one scale for the call (the reference's signature) or one per prompt (list / tuple / tensor of P), as
+        the drivers read it row by row from the prompt table (run_nudity_sdv3.py:323-329); such rows stay in one batch
+        (sdn_cfg_combine_rows).  `safree=False` with prompt strings: the prompts are encoded (negative prompt = the 17 joined
+        phrases, which the reference writes in all three of its classes) and neither the masked-prompt / concept-space encodes nor
+        the projection run -- the reference's `std` class."""
         _lib.require_gpu()
         if prompt_embeds is None and prompt is not None and self.text_front_end is not None:
             # the reference's steps 1-3 (:985-1078) for P prompts: its own negative prompt, the three encoder calls, and the inputs
@@ -93,7 +161,7 @@ class SD3SafeDenoiserPipeline:
             neg = ", ".join(SD3_NEGATIVE_PROMPT_SPACE)                        # (:996: whatever the caller passed is overwritten)
             pe, npe, pp, npp = fe.encode_prompt(prompt=prompts, negative_prompt=[neg] * len(prompts))
             prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = pe, npe, pp, npp
-            if masked_embs is None and rescaled_text_embeddings is None:
+            if safree and masked_embs is None and rescaled_text_embeddings is None:
                 masked_embs = [fe.masked_encode_prompt(p_) for p_ in prompts]
                 negspace_embs = fe.encode_negative_prompt_space(SD3_NEGATIVE_PROMPT_SPACE)
         if negative_prompt_embeds is not None:                                 # the reference's four-tensor form -> [negative | positive]
@@ -121,6 +189,17 @@ class SD3SafeDenoiserPipeline:
         dev = torch.device("cuda", torch.cuda.current_device())
         tr = self.transformer
         P = prompt_embeds.shape[0] // 2
+        # one scale for the call, or one per prompt; equal scales take the scalar kernel (same bits either way), as in pipeline.py
+        g_rows = None
+        if isinstance(guidance_scale, torch.Tensor):
+            guidance_scale = guidance_scale.detach().flatten().tolist()
+        if isinstance(guidance_scale, (list, tuple)):
+            rows = [float(g_) for g_ in guidance_scale]
+            if len(rows) != P:
+                raise _lib.SdnError(f"guidance_scale: need one value per prompt ({P}), got {len(rows)}")
+            guidance_scale = rows[0]
+            if len(set(rows)) > 1:
+                g_rows = torch.tensor(rows, dtype=torch.float32, device=dev)
         s, C_ = tr.config.sample_size, tr.config.in_channels
         if height is not None and (height // self.vae_scale_factor, (width or height) // self.vae_scale_factor) != (s, s):
             raise _lib.SdnError(f"this MMDiT plan is built for {s * 8}x{s * 8} images")
@@ -129,7 +208,7 @@ class SD3SafeDenoiserPipeline:
         # projected text to the transformer at EVERY step (:1115).  The T5 / CLIP encoders are outside this engine: the caller
         # passes either the finished `rescaled_text_embeddings` [2P,T,4096], or the first-token T5 states it takes its
         # projectors from (`masked_embs`: one [n_tokens, 4096] tensor per prompt, `negspace_embs` [n_phrases, 4096]).
-        if rescaled_text_embeddings is None and masked_embs is not None and negspace_embs is not None:
+        if safree and rescaled_text_embeddings is None and masked_embs is not None and negspace_embs is not None:
             from . import safree
             E = prompt_embeds.to(dev)
             rows = []
@@ -203,7 +282,10 @@ class SD3SafeDenoiserPipeline:
             net = self.transformer_hi if use_hi[i] else tr
             net.forward_into(x_in, t, text_of[net.dtype], pooled_of[net.dtype], vout)
             vq = vout if latents_dtype == torch.float32 else vout.to(latents_dtype).float()   # model output is fp16 in the ref
-            _lib.check(L.sdn_cfg_combine(vq.data_ptr(), P, 2, D, float(guidance_scale), v.data_ptr(), st), "sdn_cfg_combine")
+            if g_rows is not None:
+                _lib.check(L.sdn_cfg_combine_rows(vq.data_ptr(), P, 2, D, g_rows.data_ptr(), v.data_ptr(), st), "sdn_cfg_combine_rows")
+            else:
+                _lib.check(L.sdn_cfg_combine(vq.data_ptr(), P, 2, D, float(guidance_scale), v.data_ptr(), st), "sdn_cfg_combine")
             if lo <= t <= hi and repellency_processor is not None:
                 n_win += 1
                 sigma = t / 1000.0

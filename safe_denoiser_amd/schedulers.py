@@ -213,6 +213,24 @@ class FlowMatchEulerDiscreteScheduler:
         self.sigma_min, self.sigma_max = float(sig[-1]), float(sig[0])
         self.timesteps, self.sigmas, self._step_index = sig * num_train_timesteps, None, None
 
+    # -- construction from a checkpoint's scheduler_config.json (the SD-v3 `pipeline_func.from_pretrained`, run_nudity_sdv3.py:69) --
+    # as _DiscreteScheduler.from_config: accepted keys are used, a key the file lacks takes the class's own default (shift 1.0 in
+    # diffusers; SD-v3's file says 3.0), and what the step arithmetic does not implement is refused
+    @classmethod
+    def from_config(cls, config: dict):
+        name = config.get("_class_name")
+        if name is not None and name != "FlowMatchEulerDiscreteScheduler":
+            raise NotImplementedError(f"scheduler _class_name = {name!r} is not implemented (needs 'FlowMatchEulerDiscreteScheduler')")
+        if config.get("use_dynamic_shifting"):
+            raise NotImplementedError("scheduler config use_dynamic_shifting = True is not implemented")
+        return cls(num_train_timesteps=config.get("num_train_timesteps", 1000), shift=float(config.get("shift", 1.0)))
+
+    @classmethod
+    def from_pretrained(cls, model_dir: str, subfolder: str = "scheduler"):
+        from .checkpoint import read_config
+        import os
+        return cls.from_config(read_config(os.path.join(model_dir, subfolder) if subfolder else model_dir, "scheduler_config.json"))
+
     def set_timesteps(self, num_inference_steps: int, device=None):
         T, sh = self.config.num_train_timesteps, self.config.shift
         ts = torch.linspace(self.sigma_max * T, self.sigma_min * T, num_inference_steps, dtype=torch.float32)
