@@ -50,7 +50,8 @@ struct Call {
 };
 
 enum OpKind { OP_TEMB, OP_CONV_IN, OP_GEMM, OP_GN, OP_LN, OP_ATTN, OP_PATCHIFY, OP_UNPATCHIFY, OP_LATENT_MIX, OP_SOFTMAX,
-              OP_TRANSPOSE, OP_GAUSS, OP_REPEAT, OP_CLIP_EMBED, OP_MATTN, OP_ROWSTATS, OP_FFN, OP_SPLIT3,
+              OP_TRANSPOSE, OP_REPEAT = 12 /* 11 is unassigned: tests/golden/plan_digests.json pins the numbers */, OP_CLIP_EMBED, OP_MATTN,
+              OP_ROWSTATS, OP_FFN, OP_SPLIT3,
               OP_RMSNORM, OP_EMBED, OP_T5_BIAS, OP_BATTN, OP_EOS_ROWS, OP_COPY_ROWS, OP_PATCH_ROWS, OP_VISION_EMBED, OP_CLASS_ROWS,
               OP_CONV_ROWS, OP_POOL3, OP_RESIZE, OP_SPATIAL_MEAN };
 
@@ -230,6 +231,63 @@ namespace sdn_plan {
 // measured table of DESIGN 10.20 -- a form that measures slower than k_gemm_dma stays there.
 constexpr bool kK320Plain = true, kK320Ln = true, kK320Rp = true;
 
+// What one GEMM of a plan is asked to do: the operands every GEMM has (constructor), and by name everything only some have.  The
+// emitters (Builder::gemm, gemm_ex, t5_gemm, gemm_ln) take nothing else: no option reaches them from an earlier statement.  An option
+// an emitter has no form for makes the plan bad (Builder::plan_bad); res_pre and k320 are requests the chosen form's conditions may decline.
+struct GemmSpec {
+  int64_t M; int N, K;
+  Ref a, w, bias, out;
+  Ref a2; int K1 = 0;                      // second source of A: columns [K1, K)
+  Ref rowbias, rowgate; int rows_per_batch = 0, ld_row = 0;   // per-sample rows [B, ld_row] added to / multiplied into the result
+  Ref residual; int residual_bcast = 0;    // 1 = residual is [rows_per_batch, N], shared by every sample
+  int act = SDN_ACT_NONE, out_kind = SDN_OUT_BF16, n_valid = 0;
+  Ref cols;                                // column partials to emit for the GroupNorm that reads `out` (Builder::stats_of)
+  bool res_pre = false;                    // add the residual into the accumulators before the k loop (sdn_gemm_desc.res_pre) where the form allows
+  bool k320 = false;                       // may go to sdn_gemm_k320 (the C = 320 projections of transformer_body)
+  bool triple_out = false;                 // bf16x3 plan: write the triple of the result (its only reader is another x3 GEMM)
+  bool pair_out = false;                   // bf16x3 plan: write hi | lo pair rows (its only reader is sdn_attention_x3_pairs)
+  bool force_x3t = false;                  // bf16x3 plan: operand-expansion form although A is not a workspace tensor (text states)
+  bool text_kv = false;                    // K / V projection of the TEXT operand (Op::text_kv)
+  bool dyn_ldc = false;                    // the output's leading dimension is the call's out2_rs (Op::dyn_ldc)
+  bool f32_stream = false;                 // out += A W^T on the F32 residual stream `out` (sdn_gemm_desc.f32_stream)
+  GemmSpec(int64_t M_, int N_, int K_, Ref a_, Ref w_, Ref bias_, Ref out_) : M(M_), N(N_), K(K_), a(a_), w(w_), bias(bias_), out(out_) {}
+  GemmSpec& with_a2(Ref v, int k1) { a2 = v; K1 = k1; return *this; }
+  GemmSpec& with_rowbias(Ref v, int rpb, int ld) { rowbias = v; rows_per_batch = rpb; ld_row = ld; return *this; }
+  GemmSpec& with_rowgate(Ref v, int rpb, int ld) { rowgate = v; rows_per_batch = rpb; ld_row = ld; return *this; }
+  GemmSpec& with_residual(Ref v) { residual = v; return *this; }
+  GemmSpec& with_residual_bcast(Ref v, int rpb) { residual = v; residual_bcast = 1; rows_per_batch = rpb; return *this; }
+  GemmSpec& with_act(int v) { act = v; return *this; }
+  GemmSpec& with_out_kind(int v) { out_kind = v; return *this; }
+  GemmSpec& with_cols(Ref v) { cols = v; return *this; }
+  GemmSpec& with_res_pre(bool v) { res_pre = v; return *this; }
+  GemmSpec& with_k320(bool v) { k320 = v; return *this; }
+  GemmSpec& with_triple_out(bool v) { triple_out = v; return *this; }
+  GemmSpec& with_pair_out(bool v) { pair_out = v; return *this; }
+  GemmSpec& with_force_x3t(bool v) { force_x3t = v; return *this; }
+  GemmSpec& with_text_kv() { text_kv = true; return *this; }
+  GemmSpec& with_dyn_ldc() { dyn_ldc = true; return *this; }
+  GemmSpec& with_f32_stream(bool v) { f32_stream = v; return *this; }
+};
+// ... and one 3x3 convolution (Builder::conv3x3) of the map `in` to `cout` channels
+struct ConvSpec {
+  Act in; int cout, n_pad;                 // n_pad: rows of the (zero-padded) weight = the GEMM's N
+  Ref w, bias, out;
+  int stride = 1, upsample = 0, asym_pad = 0;
+  Ref rowbias; int ld_row = 0;
+  Ref residual;
+  int out_kind = SDN_OUT_BF16, n_valid = 0;
+  Ref cols;
+  bool res_pre = false;
+  ConvSpec(const Act& in_, int cout_, Ref w_, Ref bias_, Ref out_) : in(in_), cout(cout_), n_pad(cout_), w(w_), bias(bias_), out(out_) {}
+  ConvSpec& with_stride(int v, int asym = 0) { stride = v; asym_pad = asym; return *this; }
+  ConvSpec& with_upsample() { upsample = 1; return *this; }
+  ConvSpec& with_rowbias(Ref v, int ld) { rowbias = v; ld_row = ld; return *this; }
+  ConvSpec& with_residual(Ref v) { residual = v; return *this; }
+  ConvSpec& with_nchw_out(int n_pad_) { out_kind = SDN_OUT_F32_NCHW; n_valid = cout; n_pad = n_pad_; return *this; }
+  ConvSpec& with_cols(Ref v) { cols = v; return *this; }
+  ConvSpec& with_res_pre(bool v) { res_pre = v; return *this; }
+};
+
 // Emits one plan: every method appends ops to `plan` and allocates / releases activations in `arena`.  The shared emitters live in
 // sdn_plan_core.hip, the per-model blocks and build_*() in sdn_plan_unet / _mmdit / _vae / _text.hip.
 struct Builder {
@@ -245,14 +303,8 @@ struct Builder {
   Ref tproj;                 // f32 [B, tproj_total]
   int tproj_cursor = 0;      // column offset of the next resnet's slice
   Ref gn_stats;
-  Ref pending_cols;                    // set by want_stats() for the NEXT emitted GEMM
   int64_t kv_top = 0;             // bytes of persistent text K / V slots handed out so far (space SP_KV)
-  bool res_pre_next = false;      // the next gemm() adds its residual into the accumulators before the k loop (sdn_gemm_desc.res_pre)
-  bool k320_next = false;         // the next gemm() / gemm_ln() may go to sdn_gemm_k320 (set by transformer_body for the C = 320 projections)
-  bool triple_out_next = false;   // the next gemm() writes the triple of its result (its only reader is another x3 GEMM)
-  bool pair_out_next = false;     // the next gemm() writes hi | lo pair rows (a projection whose only reader is sdn_attention_x3_pairs)
-  bool plan_bad = false;          // an emitter met an inconsistency: the finished plan gets ws_bytes = -1
-  bool force_x3t_next = false;    // the next gemm() takes the operand-expansion form although its A operand is not a workspace tensor (text states)
+  bool plan_bad = false;          // an emitter met an inconsistency, or a spec asked for what its emitter cannot do: get_plan() sets ws_bytes = -1
   std::set<int64_t> pairs;        // workspace offsets that hold pair rows
   // upsampler convs that qualify for the phase form: their derived weight regions are registered by finish_up4() AFTER every real
   // parameter (no existing manifest offset moves), which then fills in the `w` of the ops emitted in that form (op >= 0)
@@ -263,31 +315,31 @@ struct Builder {
 
   // ---- parameters, activations, bf16x3 helpers and shared op emitters (sdn_plan_core.hip) -----------
   Ref param(const std::string& name, int kind, int rows, int cols, int rows_padded = 0);
+  Ref stacked(const std::vector<std::pair<std::string, int>>& members, int cols);   // {name, rows}; cols = 0: f32 vectors
   Ref stacked(const std::vector<std::string>& names, int rows_each, int cols);
-  Ref stacked_vec(const std::vector<std::string>& names, int n_each);
   Ref derived(const std::string& name, int64_t bytes);
   Act act(int64_t rows, int C, int hw = 0, int side = 0, int esz = 0);
   Act act_gn(int64_t rows, int C, int hw, int side);
-  void want_stats(const Act& out) { pending_cols = out.st_off >= 0 ? Ref{SP_WS, out.st_off} : Ref(); }
+  static Ref stats_of(const Act& out) { return out.st_off >= 0 ? Ref{SP_WS, out.st_off} : Ref(); }   // a GemmSpec's / ConvSpec's `cols`
   void drop(Act& t);
   static Ref R(const Act& t) { return Ref{SP_WS, t.off}; }
   Ref x3_weight(Ref w, int rows, int cols, int group);
   Act split3(Ref a, Ref a2, int64_t rows, int c1, int c2, int hw = 0, int side = 0);
   bool x3t_on(const Ref& a) const { return x3t && !x3t_hold && a.space == SP_WS; }
-  void gemm(int64_t M, int N, int K, Ref a, Ref w, Ref bias, Ref out, int act_ = SDN_ACT_NONE, Ref residual = Ref(),
-            int out_kind = SDN_OUT_BF16, int n_valid = 0, Ref a2 = Ref(), int K1 = 0, Ref rowbias = Ref(),
-            int rows_per_batch = 0, int ld_rowbias = 0);
-  void push_gemm(Op& o);
-  void conv3x3(const Act& in, int cout, int n_pad, Ref w, Ref bias, Ref out, int stride, int upsample, Ref residual,
-               Ref rowbias, int ld_rowbias, int out_kind = SDN_OUT_BF16, int n_valid = 0, int asym_pad = 0);
+  void emit(Op& o, bool attn = false);
+  std::vector<Ref> derived_job(const std::vector<std::pair<std::string, int64_t>>& regions, sdn_unet::FoldJob job);
+  void gemm(const GemmSpec& s);
+  void push_gemm(Op& o, Ref cols);
+  void conv3x3(const ConvSpec& s);
   void groupnorm(const Act& x, const Act* x2, float eps, int silu, Ref gamma, Ref beta, const Act& out);
   void layernorm(const Act& x, Ref gamma, Ref beta, const Act& out);
   void repeat(const Act& in, const Act& out, int rep);
   void attention(Ref q, Ref k, Ref v, Ref out, int nq, int nk, int C, int ldq, int ldk, int ldv, bool kv_pairs = false);
 
   // ---- SD-v1.4 UNet (sdn_plan_unet.hip) --------------------------------------------------------------
-  void gemm_ln(const Act& x, int64_t rows, int N, int K, const std::string& wname, Ref w, Ref gamma, Ref beta, Ref bias,
-               Ref out, int act_, bool prepass);
+  std::vector<Ref> ln_fold_regions(const std::string& wname, Ref w, Ref gamma, Ref beta, Ref bias, int N, int K);
+  void row_stats(Ref x, int64_t rows, int C, const Act& st);
+  void gemm_ln(const GemmSpec& s, const std::string& wname, Ref gamma, Ref beta, bool prepass);
   Act resnet(const std::string& pfx, Act& x, Act* skip, int cout);
   Act transformer(const std::string& pfx, Act& x);
   void transformer_body(const std::string& pfx, Act& x, const Act& out, int64_t text_off, int rep = 1,
@@ -296,8 +348,7 @@ struct Builder {
   void build();
 
   // ---- SD-v3 MMDiT (sdn_plan_mmdit.hip) --------------------------------------------------------------
-  void gemm_ex(int64_t M, int N, int K, Ref a, Ref w, Ref bias, Ref out, int act_, Ref residual, int out_kind,
-               Ref rowbias, Ref rowgate, int rows_per_batch, int ld_row, int residual_bcast = 0);
+  void gemm_ex(const GemmSpec& s);
   void ln_mod(const Act& x, int64_t rows, int rows_per_batch, Ref scale, Ref shift, int ld, const Act& out);
   Ref fcol(int col) const { return Ref{SP_WS, tproj.off + (int64_t)col * 4}; }   // column of the stacked adaLN output
   void build_mmdit();
@@ -312,7 +363,7 @@ struct Builder {
   // ---- CLIP (plain and projected) and T5 text encoders (sdn_plan_text.hip) ---------------------------
   void build_clip();
   Ref glu_pair(const std::string& value_name, const std::string& gate_name, int F, int K);
-  void t5_gemm(int64_t M, int N, int K, Ref a, Ref w, Ref out, int act_, bool into_stream);
+  void t5_gemm(const GemmSpec& s);
   void t5_rmsnorm(Ref x, bool x_f32, int64_t rows, int C, Ref w, Ref out);
   void build_t5();
 

@@ -14,6 +14,10 @@ template <class F, class V> static void set_plan_toggle(sdn_unet* u, F sdn_unet:
   u->plans.clear();
 }
 
+// fp32-storage modes (dtype 2 / 3) run the plain operator chain (sdn_f32.hip): no statistics from the producers, no folded LayerNorm,
+// no fused feed-forward.  A creator calls this before its first get_plan().
+static void plain_chain_for_f32(sdn_unet* u, int dtype) { if (dtype >= 2) u->gn_fuse = u->ln_fold = u->ff_fuse = false; }
+
 extern "C" {
 
 int sdn_unet_create(const sdn_unet_config* cfg, sdn_unet** out) {
@@ -37,7 +41,7 @@ int sdn_unet_create(const sdn_unet_config* cfg, sdn_unet** out) {
   }
   sdn_unet* u = new sdn_unet();
   u->cfg = *cfg;
-  if (cfg->dtype >= 2) { u->gn_fuse = false; u->ln_fold = false; u->ff_fuse = false; }   // fp32-storage modes: the plain operator chain (sdn_f32.hip)
+  plain_chain_for_f32(u, cfg->dtype);
   get_plan(u, cfg->latent_repeat > 1 ? cfg->latent_repeat : 1);   // registers the parameter manifest (batch-independent)
   *out = u;
   return SDN_OK;
@@ -77,10 +81,10 @@ int sdn_vae_decoder_create(const sdn_vae_config* cfg, sdn_unet** out) {
   sdn_unet* u = new sdn_unet();
   memset(&u->cfg, 0, sizeof(u->cfg));
   u->cfg.norm_groups = cfg->norm_groups;
-  // fp32-storage modes: the plain operator chain.  gn_fuse off = no activation carries a statistics slot (act_gn), so want_stats
-  // selects nothing and every GroupNorm computes its own; the phase-form upsamplers are a 16-bit UNet form (Builder::conv3x3) and
-  // split-K stays off (sdn_unet_set_split_k refuses these modes)
-  if (cfg->dtype >= 2) { u->gn_fuse = false; u->ln_fold = false; u->ff_fuse = false; }
+  // gn_fuse off = no activation carries a statistics slot (act_gn), so stats_of() names nothing and every GroupNorm computes its
+  // own; the phase-form upsamplers are a 16-bit UNet form (Builder::conv3x3) and split-K stays off (sdn_unet_set_split_k refuses
+  // these modes)
+  plain_chain_for_f32(u, cfg->dtype);
   u->vcfg = *cfg;
   u->kind = VAE_DECODER;
   get_plan(u, 1);
@@ -110,7 +114,7 @@ int sdn_clip_create(const sdn_clip_config* cfg, sdn_unet** out) {
     return SDN_E_INVALID;
   sdn_unet* u = new sdn_unet();
   memset(&u->cfg, 0, sizeof(u->cfg));
-  if (cfg->dtype >= 2) { u->gn_fuse = false; u->ln_fold = false; u->ff_fuse = false; }   // fp32-storage modes: the plain operator chain
+  plain_chain_for_f32(u, cfg->dtype);
   u->ccfg = *cfg;
   u->kind = CLIP;
   get_plan(u, 1);
@@ -130,7 +134,7 @@ int sdn_clip_proj_create(const sdn_clip_proj_config* cfg, sdn_unet** out) {
     return SDN_E_INVALID;
   sdn_unet* u = new sdn_unet();
   memset(&u->cfg, 0, sizeof(u->cfg));
-  if (cfg->dtype >= 2) { u->gn_fuse = false; u->ln_fold = false; u->ff_fuse = false; }   // fp32-storage modes: the plain operator chain
+  plain_chain_for_f32(u, cfg->dtype);
   u->pcfg = *cfg;
   u->ccfg.vocab_size = cfg->vocab_size; u->ccfg.hidden_size = cfg->hidden_size; u->ccfg.intermediate_size = cfg->intermediate_size;
   u->ccfg.num_layers = cfg->num_layers; u->ccfg.num_heads = cfg->num_heads; u->ccfg.max_position_embeddings = cfg->max_position_embeddings;

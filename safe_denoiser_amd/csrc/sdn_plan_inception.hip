@@ -38,7 +38,7 @@ void Builder::inception_conv(const std::string& name, const Act& in, int cout, i
     Op o; o.kind = OP_CONV_ROWS; o.a = R(in); o.out = R(pr); o.batch = B; o.hw = in.side; o.c1 = cin; o.c2 = kpad;
     o.kh = kh; o.kw = kw; o.sh = o.sw = stride; o.ph = ph; o.pw = pw; o.rows = M;
     o.bytes = 4.0 * ((double)B * in.side * in.side * cin + (double)M * kpad);
-    snprintf(o.label, sizeof(o.label), "k_patch_rows_f32"); plan->ops.push_back(o);
+    snprintf(o.label, sizeof(o.label), "k_patch_rows_f32"); emit(o);
     a = R(pr);
   }
   Op o; o.kind = OP_GEMM; memset(&o.gd, 0, sizeof(o.gd));
@@ -47,7 +47,7 @@ void Builder::inception_conv(const std::string& name, const Act& in, int cout, i
   o.a = a; o.w = w; o.bias = bias; o.out = Ref{SP_WS, out.off + (int64_t)c0 * 4};
   o.flops = 2.0 * (double)M * cout * (double)(kh * kw * cin);               // the convolution's own count: padding columns are not work
   o.bytes = 4.0 * ((double)M * kpad + (double)npad * kpad + (double)M * cout);
-  snprintf(o.label, sizeof(o.label), "k_gemm_f32"); plan->ops.push_back(o); plan->flops += o.flops;
+  snprintf(o.label, sizeof(o.label), "k_gemm_f32"); emit(o);
   if (pr.off >= 0) drop(pr);                                                // stream order: the next op may reuse it
 }
 
@@ -64,7 +64,7 @@ void Builder::inception_pool(int mode, const Act& in, int stride, int pad, const
   Op o; o.kind = OP_POOL3; o.mod = mode; o.a = R(in); o.out = R(out); o.batch = B; o.hw = in.side; o.c1 = in.C; o.sh = stride; o.ph = pad;
   o.ldo = out.C; o.c2 = c0; o.rows = (int64_t)B * so * so;
   o.bytes = 4.0 * ((double)B * in.side * in.side * in.C + (double)o.rows * in.C);
-  snprintf(o.label, sizeof(o.label), "k_pool3_f32"); plan->ops.push_back(o);
+  snprintf(o.label, sizeof(o.label), "k_pool3_f32"); emit(o);
 }
 
 void Builder::build_inception() {
@@ -81,7 +81,7 @@ void Builder::build_inception() {
   Act x = map(S, 3);
   { Op o; o.kind = OP_RESIZE; o.a = Ref{SP_IN, 0}; o.out = R(x); o.batch = B; o.hw = S; o.scale = c.normalize_input ? 2.f : 1.f;
     o.eps = c.normalize_input ? -1.f : 0.f; o.rows = (int64_t)B * S * S; o.bytes = 2.0 * 12.0 * B * S * S;
-    snprintf(o.label, sizeof(o.label), "k_resize_bilinear_f32"); plan->ops.push_back(o); }
+    snprintf(o.label, sizeof(o.label), "k_resize_bilinear_f32"); emit(o); }
 
   // ---- stem: Conv2d_1a_3x3 .. Conv2d_4a_3x3 with the two max pools ----
   Act t = inception_conv_new("Conv2d_1a_3x3", x, 32, 3, 3, 2); drop(x);
@@ -175,9 +175,9 @@ void Builder::build_inception() {
   // ---- AdaptiveAvgPool2d(1) -> features [B, 2048] ----
   { Op o; o.kind = OP_SPATIAL_MEAN; o.a = R(x); o.out = Ref{SP_OUT, 0}; o.batch = B; o.hw = x.side * x.side; o.c1 = x.C; o.rows = B;
     o.bytes = 4.0 * ((double)B * o.hw * x.C + (double)B * x.C);
-    snprintf(o.label, sizeof(o.label), "k_spatial_mean_f32"); plan->ops.push_back(o); }
+    snprintf(o.label, sizeof(o.label), "k_spatial_mean_f32"); emit(o); }
   drop(x);
-  plan->ws_bytes = plan_bad ? -1 : arena.peak;
+  plan->ws_bytes = arena.peak;
 }
 
 }  // namespace sdn_plan

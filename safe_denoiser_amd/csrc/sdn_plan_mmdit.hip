@@ -10,27 +10,29 @@ namespace sdn_plan {
 //  models/sdv3/safe_denoiser_pipeline.py:1120-1127.  Two token streams (image, text) with adaLN-zero
 //  modulation from (timestep, pooled text); joint attention over both streams without concatenating them.
 // =====================================================================================================
-void Builder::gemm_ex(int64_t M, int N, int K, Ref a, Ref w, Ref bias, Ref out, int act_, Ref residual, int out_kind,
-                      Ref rowbias, Ref rowgate, int rows_per_batch, int ld_row, int residual_bcast) {
+// The MMDiT's GEMM: per-sample row bias / gate and a broadcast residual; bytes at the storage width, the residual not charged.
+void Builder::gemm_ex(const GemmSpec& s) {
+  if (s.a2.space != SP_NONE || s.n_valid || s.res_pre || s.k320 || s.triple_out || s.pair_out || s.force_x3t || s.text_kv || s.dyn_ldc || s.f32_stream)
+    plan_bad = true;                                           // forms of gemm() / t5_gemm()
   Op o; o.kind = OP_GEMM; memset(&o.gd, 0, sizeof(o.gd));
-  o.gd.M = (int)M; o.gd.N = N; o.gd.K = K; o.gd.a_mode = SDN_A_PLAIN; o.gd.act = act_; o.gd.out_kind = out_kind;
-  o.gd.rows_per_batch = rows_per_batch; o.gd.ld_rowbias = ld_row; o.gd.ld_rowgate = ld_row;
-  o.gd.residual_bcast = residual_bcast;
-  o.a = a; o.w = w; o.bias = bias; o.rowbias = rowbias; o.rowgate = rowgate; o.residual = residual; o.out = out;
-  o.flops = 2.0 * (double)M * N * K;
-  o.bytes = es * ((double)M * K + (double)N * K + (double)M * N);
+  o.gd.M = (int)s.M; o.gd.N = s.N; o.gd.K = s.K; o.gd.a_mode = SDN_A_PLAIN; o.gd.act = s.act; o.gd.out_kind = s.out_kind;
+  o.gd.rows_per_batch = s.rows_per_batch; o.gd.ld_rowbias = s.ld_row; o.gd.ld_rowgate = s.ld_row;
+  o.gd.residual_bcast = s.residual_bcast;
+  o.a = s.a; o.w = s.w; o.bias = s.bias; o.rowbias = s.rowbias; o.rowgate = s.rowgate; o.residual = s.residual; o.out = s.out;
+  o.flops = 2.0 * (double)s.M * s.N * s.K;
+  o.bytes = es * ((double)s.M * s.K + (double)s.N * s.K + (double)s.M * s.N);
   if (es == 4)                      // MMDiT fp32-storage plans: sdn_gemm_f32, or sdn_gemm_x3 (its f32 tile below 64 rows)
-    snprintf(o.label, sizeof(o.label), (u->mcfg.dtype == 3 && M >= 64) ? "k_gemm_x3" : "k_gemm_f32");
+    snprintf(o.label, sizeof(o.label), (u->mcfg.dtype == 3 && s.M >= 64) ? "k_gemm_x3" : "k_gemm_f32");
   else
-    snprintf(o.label, sizeof(o.label), "k_gemm<%d>", sdn_gemm_pick_tile((int)M, N, K, act_, residual.space != SP_NONE || rowgate.space != SP_NONE));
-  push_gemm(o);
+    snprintf(o.label, sizeof(o.label), "k_gemm<%d>", sdn_gemm_pick_tile((int)s.M, s.N, s.K, s.act, s.residual.space != SP_NONE || s.rowgate.space != SP_NONE));
+  push_gemm(o, s.cols);
 }
 void Builder::ln_mod(const Act& x, int64_t rows, int rows_per_batch, Ref scale, Ref shift, int ld, const Act& out) {
   Op o; o.kind = OP_LN; o.a = R(x); o.rows = rows; o.c1 = x.C; o.eps = 1e-6f; o.w = scale; o.bias = shift; o.out = R(out);
   o.mod = 1; o.ld_mod = ld; o.hw = rows_per_batch;
   o.bytes = 2.0 * es * (double)rows * x.C;
   snprintf(o.label, sizeof(o.label), es == 4 ? "k_layernorm_mod_f32" : "k_layernorm");
-  plan->ops.push_back(o);
+  emit(o);
 }
 
 void Builder::build_mmdit() {
@@ -53,61 +55,46 @@ void Builder::build_mmdit() {
   // column layout per block i: img 6C at col_img[i], ctx 6C (2C for the last, context_pre_only block) at col_ctx[i]
   std::vector<int> col_img(L), col_ctx(L);
   int total = 0;
-  Ref adw, adb;
-  {
-    std::vector<std::pair<std::string, int>> mods;
-    for (int i = 0; i < L; ++i) {
-      col_img[i] = total; mods.push_back({nm(i, "norm1.linear"), 6 * C}); total += 6 * C;
-      const int nc = (i == L - 1) ? 2 * C : 6 * C;
-      col_ctx[i] = total; mods.push_back({nm(i, "norm1_context.linear"), nc}); total += nc;
-    }
-    const int col_out = total; mods.push_back({"norm_out.linear", 2 * C}); total += 2 * C;
-    (void)col_out;
-    int64_t expect = -1;
-    for (size_t j = 0; j < mods.size(); ++j) {
-      Ref r = param(mods[j].first + ".weight", SDN_P_MAT, mods[j].second, C);
-      if (j == 0) adw = r; else if (r.off != expect) { fprintf(stderr, "libsdn: adaLN weights not contiguous\n"); abort(); }
-      expect = r.off + (int64_t)mods[j].second * C * es;
-    }
-    expect = -1;
-    for (size_t j = 0; j < mods.size(); ++j) {
-      Ref r = param(mods[j].first + ".bias", SDN_P_VEC_F32, mods[j].second, 0);
-      if (j == 0) adb = r; else if (r.off != expect) { fprintf(stderr, "libsdn: adaLN biases not contiguous\n"); abort(); }
-      expect = r.off + (int64_t)mods[j].second * 4;
-    }
+  std::vector<std::pair<std::string, int>> lins, adws, adbs;
+  for (int i = 0; i < L; ++i) {
+    col_img[i] = total; lins.push_back({nm(i, "norm1.linear"), 6 * C}); total += 6 * C;
+    const int nc = (i == L - 1) ? 2 * C : 6 * C;
+    col_ctx[i] = total; lins.push_back({nm(i, "norm1_context.linear"), nc}); total += nc;
   }
+  lins.push_back({"norm_out.linear", 2 * C}); total += 2 * C;                       // at column total - 2C
+  for (const auto& m : lins) { adws.push_back({m.first + ".weight", m.second}); adbs.push_back({m.first + ".bias", m.second}); }
+  Ref adw = stacked(adws, C), adb = stacked(adbs, 0);
   u->tproj_total = total;
 
   // ---- conditioning: silu(time_emb + pooled_emb) -> all modulation vectors ----
   plan->tscalar_off = arena.alloc(256);
   Act tsin = act(B, c.time_dim);
-  { Op o; o.kind = OP_TEMB; o.batch = B; o.c1 = c.time_dim; o.out = R(tsin); snprintf(o.label, sizeof(o.label), es == 4 ? "k_temb_f32" : "k_temb");
-    plan->ops.push_back(o); }
+  { Op o; o.kind = OP_TEMB; o.batch = B; o.c1 = c.time_dim; o.out = R(tsin); snprintf(o.label, sizeof(o.label), es == 4 ? "k_temb_f32" : "k_temb"); emit(o); }
   Act th = act(B, C);
-  gemm_ex(B, C, c.time_dim, R(tsin), t1w, t1b, R(th), SDN_ACT_SILU, Ref(), SDN_OUT_BF16, Ref(), Ref(), 0, 0);
+  gemm_ex(GemmSpec(B, C, c.time_dim, R(tsin), t1w, t1b, R(th)).with_act(SDN_ACT_SILU));
   drop(tsin);
   Act temb = act(B, C, 0, 0, 4);                                                 // f32 [B, C]
-  gemm_ex(B, C, C, R(th), t2w, t2b, R(temb), SDN_ACT_NONE, Ref(), SDN_OUT_F32, Ref(), Ref(), 0, 0);
+  gemm_ex(GemmSpec(B, C, C, R(th), t2w, t2b, R(temb)).with_out_kind(SDN_OUT_F32));
   drop(th);
   Act ph = act(B, C);
-  gemm_ex(B, C, c.pooled_dim, Ref{SP_POOLED, 0}, p1w, p1b, R(ph), SDN_ACT_SILU, Ref(), SDN_OUT_BF16, Ref(), Ref(), 0, 0);
+  gemm_ex(GemmSpec(B, C, c.pooled_dim, Ref{SP_POOLED, 0}, p1w, p1b, R(ph)).with_act(SDN_ACT_SILU));
   Act scond = act(B, C);                                                         // silu(time_emb + pooled_emb)
-  gemm_ex(B, C, C, R(ph), p2w, p2b, R(scond), SDN_ACT_SILU, Ref(), SDN_OUT_BF16, R(temb), Ref(), 1, C);
+  gemm_ex(GemmSpec(B, C, C, R(ph), p2w, p2b, R(scond)).with_act(SDN_ACT_SILU).with_rowbias(R(temb), 1, C));
   drop(ph); drop(temb);
   Act mods = act(B, total, 0, 0, 4);
   tproj = R(mods);
-  gemm_ex(B, total, C, R(scond), adw, adb, R(mods), SDN_ACT_NONE, Ref(), SDN_OUT_F32, Ref(), Ref(), 0, 0);
+  gemm_ex(GemmSpec(B, total, C, R(scond), adw, adb, R(mods)).with_out_kind(SDN_OUT_F32));
   drop(scond);
 
   // ---- token streams ----
   Act patches = act((int64_t)B * N, KP);
   { Op o; o.kind = OP_PATCHIFY; o.batch = B; o.c1 = c.in_channels; o.hw = S; o.patch = ps; o.a = Ref{SP_IN, 0}; o.out = R(patches);
-    o.bytes = (double)B * N * KP * (4.0 + es); snprintf(o.label, sizeof(o.label), es == 4 ? "k_patchify_f32" : "k_patchify"); plan->ops.push_back(o); }
+    o.bytes = (double)B * N * KP * (4.0 + es); snprintf(o.label, sizeof(o.label), es == 4 ? "k_patchify_f32" : "k_patchify"); emit(o); }
   Act x = act((int64_t)B * N, C, N);
-  gemm_ex((int64_t)B * N, C, KP, R(patches), pew, peb, R(x), SDN_ACT_NONE, pos, SDN_OUT_BF16, Ref(), Ref(), N, 0, 1);
+  gemm_ex(GemmSpec((int64_t)B * N, C, KP, R(patches), pew, peb, R(x)).with_residual_bcast(pos, N));
   drop(patches);
   Act ctx = act((int64_t)B * T, C, T);
-  gemm_ex((int64_t)B * T, C, c.joint_dim, Ref{SP_TEXT, 0}, cew, ceb, R(ctx), SDN_ACT_NONE, Ref(), SDN_OUT_BF16, Ref(), Ref(), 0, 0);
+  gemm_ex(GemmSpec((int64_t)B * T, C, c.joint_dim, Ref{SP_TEXT, 0}, cew, ceb, R(ctx)));
 
   for (int i = 0; i < L; ++i) {
     const bool last = (i == L - 1);
@@ -128,8 +115,8 @@ void Builder::build_mmdit() {
     if (last) ln_mod(ctx, (int64_t)B * T, T, fcol(cc + 0 * C), fcol(cc + 1 * C), total, cn);
     else ln_mod(ctx, (int64_t)B * T, T, fcol(cc + 1 * C), fcol(cc + 0 * C), total, cn);
     Act qx = act((int64_t)B * N, 3 * C, N), qc = act((int64_t)B * T, 3 * C, T);
-    gemm_ex((int64_t)B * N, 3 * C, C, R(xn), qkvw, qkvb, R(qx), SDN_ACT_NONE, Ref(), SDN_OUT_BF16, Ref(), Ref(), 0, 0);
-    gemm_ex((int64_t)B * T, 3 * C, C, R(cn), aqkvw, aqkvb, R(qc), SDN_ACT_NONE, Ref(), SDN_OUT_BF16, Ref(), Ref(), 0, 0);
+    gemm_ex(GemmSpec((int64_t)B * N, 3 * C, C, R(xn), qkvw, qkvb, R(qx)));
+    gemm_ex(GemmSpec((int64_t)B * T, 3 * C, C, R(cn), aqkvw, aqkvb, R(qc)));
     drop(xn); drop(cn);
     Act ax = act((int64_t)B * N, C, N), ac = act((int64_t)B * T, C, T);
     {
@@ -141,21 +128,20 @@ void Builder::build_mmdit() {
       o.bytes = es * (double)B * (N + T) * C * 4.0;
       if (es == 4) snprintf(o.label, sizeof(o.label), u->mcfg.dtype == 3 ? "k_attention_x3/seg" : "k_attention_f32/seg");
       else snprintf(o.label, sizeof(o.label), "k_attn<%d>", o.hd);
-      plan->ops.push_back(o);
-      plan->flops += o.flops; plan->attn_flops += o.flops;
+      emit(o);
     }
     drop(qx); drop(qc);
     // image stream: x += gate_msa * to_out(attn);  x += gate_mlp * ff(LNmod(x))
     Act x2 = act((int64_t)B * N, C, N);
-    gemm_ex((int64_t)B * N, C, C, R(ax), ow, ob, R(x2), SDN_ACT_NONE, R(x), SDN_OUT_BF16, Ref(), fcol(ci + 2 * C), N, total);
+    gemm_ex(GemmSpec((int64_t)B * N, C, C, R(ax), ow, ob, R(x2)).with_residual(R(x)).with_rowgate(fcol(ci + 2 * C), N, total));
     drop(ax); drop(x);
     Act xm = act((int64_t)B * N, C, N);
     ln_mod(x2, (int64_t)B * N, N, fcol(ci + 4 * C), fcol(ci + 3 * C), total, xm);
     Act hx = act((int64_t)B * N, 4 * C, N);
-    gemm_ex((int64_t)B * N, 4 * C, C, R(xm), f1w, f1b, R(hx), SDN_ACT_GELU_TANH, Ref(), SDN_OUT_BF16, Ref(), Ref(), 0, 0);
+    gemm_ex(GemmSpec((int64_t)B * N, 4 * C, C, R(xm), f1w, f1b, R(hx)).with_act(SDN_ACT_GELU_TANH));
     drop(xm);
     Act x3 = act((int64_t)B * N, C, N);
-    gemm_ex((int64_t)B * N, C, 4 * C, R(hx), f2w, f2b, R(x3), SDN_ACT_NONE, R(x2), SDN_OUT_BF16, Ref(), fcol(ci + 5 * C), N, total);
+    gemm_ex(GemmSpec((int64_t)B * N, C, 4 * C, R(hx), f2w, f2b, R(x3)).with_residual(R(x2)).with_rowgate(fcol(ci + 5 * C), N, total));
     drop(hx); drop(x2);
     x = x3;
     // text stream (skipped in the last block: context_pre_only)
@@ -164,15 +150,15 @@ void Builder::build_mmdit() {
       Ref g1w = param(nm(i, "ff_context.net.0.proj.weight"), SDN_P_MAT, 4 * C, C), g1b = param(nm(i, "ff_context.net.0.proj.bias"), SDN_P_VEC_F32, 4 * C, 0);
       Ref g2w = param(nm(i, "ff_context.net.2.weight"), SDN_P_MAT, C, 4 * C), g2b = param(nm(i, "ff_context.net.2.bias"), SDN_P_VEC_F32, C, 0);
       Act c2 = act((int64_t)B * T, C, T);
-      gemm_ex((int64_t)B * T, C, C, R(ac), aow, aob, R(c2), SDN_ACT_NONE, R(ctx), SDN_OUT_BF16, Ref(), fcol(cc + 2 * C), T, total);
+      gemm_ex(GemmSpec((int64_t)B * T, C, C, R(ac), aow, aob, R(c2)).with_residual(R(ctx)).with_rowgate(fcol(cc + 2 * C), T, total));
       drop(ctx);
       Act cm = act((int64_t)B * T, C, T);
       ln_mod(c2, (int64_t)B * T, T, fcol(cc + 4 * C), fcol(cc + 3 * C), total, cm);
       Act hc = act((int64_t)B * T, 4 * C, T);
-      gemm_ex((int64_t)B * T, 4 * C, C, R(cm), g1w, g1b, R(hc), SDN_ACT_GELU_TANH, Ref(), SDN_OUT_BF16, Ref(), Ref(), 0, 0);
+      gemm_ex(GemmSpec((int64_t)B * T, 4 * C, C, R(cm), g1w, g1b, R(hc)).with_act(SDN_ACT_GELU_TANH));
       drop(cm);
       Act c3 = act((int64_t)B * T, C, T);
-      gemm_ex((int64_t)B * T, C, 4 * C, R(hc), g2w, g2b, R(c3), SDN_ACT_NONE, R(c2), SDN_OUT_BF16, Ref(), fcol(cc + 5 * C), T, total);
+      gemm_ex(GemmSpec((int64_t)B * T, C, 4 * C, R(hc), g2w, g2b, R(c3)).with_residual(R(c2)).with_rowgate(fcol(cc + 5 * C), T, total));
       drop(hc); drop(c2);
       ctx = c3;
     } else {
@@ -188,10 +174,10 @@ void Builder::build_mmdit() {
   const int PO = ps * ps * c.out_channels;
   Ref pw = param("proj_out.weight", SDN_P_MAT, PO, C), pb = param("proj_out.bias", SDN_P_VEC_F32, PO, 0);
   Act tok = act((int64_t)B * N, PO, N, 0, 4);
-  gemm_ex((int64_t)B * N, PO, C, R(xo), pw, pb, R(tok), SDN_ACT_NONE, Ref(), SDN_OUT_F32, Ref(), Ref(), 0, 0);
+  gemm_ex(GemmSpec((int64_t)B * N, PO, C, R(xo), pw, pb, R(tok)).with_out_kind(SDN_OUT_F32));
   drop(xo);
   { Op o; o.kind = OP_UNPATCHIFY; o.batch = B; o.c1 = c.out_channels; o.hw = S; o.patch = ps; o.a = R(tok); o.out = Ref{SP_OUT, 0};
-    o.bytes = (double)B * N * PO * 8.0; snprintf(o.label, sizeof(o.label), "k_unpatchify"); plan->ops.push_back(o); }
+    o.bytes = (double)B * N * PO * 8.0; snprintf(o.label, sizeof(o.label), "k_unpatchify"); emit(o); }
   drop(tok);
   drop(mods);
   plan->ws_bytes = arena.peak;

@@ -309,6 +309,8 @@ static int launch_op_16(const sdn_unet* u, const Op& o, const Call& P, bool f16,
       rc = (f16 ? sdn_attention_f16 : sdn_attention_bf16)(P(o.a), P(o.k), P(o.v), (void*)P(o.out), o.batch, o.heads, o.nq, o.nk, o.hd, o.ldq,
                               o.ldk, o.ldv, o.ldo, o.scale, stream);
       break;
+    default:
+      rc = SDN_E_INVALID;
   }
   return rc;
 }
@@ -419,6 +421,46 @@ extern "C" int sdn_debug_profile_ops(sdn_unet* u, double* out, char* labels, int
     memcpy(labels + n * 24, o.label, 24);
   }
   return n;
+}
+
+// Undeclared debug hook (tools/plan_fingerprint.py, tests/test_plan_digests.py): 64-bit FNV-1a over everything the planner decided for
+// (batch, n) -- the plan header, every op field by field in declaration order (never a whole Op: padding), then the handle's fold
+// jobs.  gd is hashed for OP_GEMM only: no other emitter initialises it.  Host only.
+namespace {
+struct Fnv {
+  uint64_t h = 1469598103934665603ull;
+  void bytes(const void* p, size_t n) { for (size_t i = 0; i < n; ++i) { h ^= ((const unsigned char*)p)[i]; h *= 1099511628211ull; } }
+  template <class T> void operator()(const T& v) { bytes(&v, sizeof(T)); }     // scalars only
+  void operator()(const Ref& r) { (*this)(r.space); (*this)(r.off); }
+};
+}  // namespace
+extern "C" int sdn_debug_plan_digest(sdn_unet* u, int32_t batch, int32_t n, uint64_t* out) {
+  if (!u || !out || batch <= 0) return SDN_E_INVALID;
+  const Plan* p = get_plan(u, batch, n);
+  Fnv f;
+  f(p->batch); f(p->tscalar_off); f(p->ws_bytes); f(p->kv_base); f(p->flops); f(p->attn_flops); f((uint64_t)p->ops.size());
+  static_assert(sizeof(sdn_gemm_desc) == 25 * sizeof(int32_t), "sdn_gemm_desc: 25 int32 fields");
+  for (const Op& o : p->ops) {
+    f(o.kind);
+    if (o.kind == OP_GEMM) for (int i = 0; i < 25; ++i) f(((const int32_t*)&o.gd)[i]);
+    f(o.a); f(o.a2); f(o.w); f(o.bias); f(o.rowbias); f(o.rowgate); f(o.residual); f(o.out); f(o.aux);
+    f(o.q2); f(o.k2); f(o.v2); f(o.out2);
+    f(o.col); f(o.cols1); f(o.cols2);
+    f(o.ln_c); f(o.ln_d); f(o.ln_stats);
+    f(o.ln); f(o.text_kv); f(o.x3t); f(o.pair_in); f(o.tri_out); f(o.dyn_ldc); f(o.k320);
+    f(o.n1); f(o.mod); f(o.ld_mod); f(o.patch);
+    f(o.batch); f(o.hw); f(o.c1); f(o.c2); f(o.groups); f(o.silu);
+    f(o.eps); f(o.rows);
+    f(o.heads); f(o.nq); f(o.nk); f(o.hd); f(o.ldq); f(o.ldk); f(o.ldv); f(o.ldo);
+    f(o.scale); f(o.k); f(o.v);
+    f(o.kh); f(o.kw); f(o.sh); f(o.sw); f(o.ph); f(o.pw);
+    f.bytes(o.label, sizeof(o.label)); f(o.flops); f(o.bytes);
+  }
+  for (const sdn_unet::FoldJob& j : u->fold_jobs) {
+    f(j.w); f(j.gamma); f(j.beta); f(j.bias); f(j.wf); f(j.c); f(j.d); f(j.rows); f(j.cols); f(j.kind); f(j.group);
+  }
+  *out = f.h;
+  return SDN_OK;
 }
 
 extern "C" int sdn_unet_profile_read(sdn_unet* u, sdn_profile_row* rows, int32_t max_rows) {

@@ -29,35 +29,42 @@
 
 namespace sdn_plan {
 
-// LayerNorm(x; gamma, beta) -> GEMM(W, bias) with the norm folded into the GEMM (sdn_gemm_ln_*).  Registers the derived
-// weight regions once; `prepass` = row statistics from a read-only pass instead of inside the kernel (wide N).
-void Builder::gemm_ln(const Act& x, int64_t rows, int N, int K, const std::string& wname, Ref w, Ref gamma, Ref beta, Ref bias,
-                      Ref out, int act_, bool prepass) {
-  const bool fresh = u->param_index.find(wname + "#ln") == u->param_index.end();
-  Ref wf = derived(wname + "#ln", (int64_t)N * K * 2), c = derived(wname + "#ln_c", (int64_t)N * 4), d = derived(wname + "#ln_d", (int64_t)N * 4);
-  if (fresh) u->fold_jobs.push_back({w.off, gamma.off, beta.off, bias.space == SP_NONE ? -1 : bias.off, wf.off, c.off, d.off, N, K});
+// the derived regions {folded weight, c, d} of a linear [N, K] behind a LayerNorm, and the job that fills them
+std::vector<Ref> Builder::ln_fold_regions(const std::string& wname, Ref w, Ref gamma, Ref beta, Ref bias, int N, int K) {
+  return derived_job({{wname + "#ln", (int64_t)N * K * 2}, {wname + "#ln_c", (int64_t)N * 4}, {wname + "#ln_d", (int64_t)N * 4}},
+                     {w.off, gamma.off, beta.off, bias.space == SP_NONE ? -1 : bias.off, -1, -1, -1, N, K});
+}
+// row statistics of x [rows, C] by a read-only pass, for a folded LayerNorm that does not take them from its own fragments
+void Builder::row_stats(Ref x, int64_t rows, int C, const Act& st) {
+  Op o; o.kind = OP_ROWSTATS; o.a = x; o.rows = rows; o.c1 = C; o.eps = 1e-5f; o.out = R(st);
+  o.bytes = 2.0 * rows * C; snprintf(o.label, sizeof(o.label), "k_row_stats");
+  emit(o);
+}
+// LayerNorm(a; gamma, beta) -> GEMM(w, bias) with the norm folded into the GEMM (sdn_gemm_ln_*): s names the linear's own a / w /
+// bias (the op runs on the folded forms); beyond them it can take act and k320.  `prepass` = row statistics from a read-only pass
+// instead of inside the kernel (wide N).
+void Builder::gemm_ln(const GemmSpec& s, const std::string& wname, Ref gamma, Ref beta, bool prepass) {
+  if (s.cols.space != SP_NONE || s.a2.space != SP_NONE || s.residual.space != SP_NONE || s.rowbias.space != SP_NONE || s.rowgate.space != SP_NONE ||
+      s.out_kind != SDN_OUT_BF16 || s.n_valid || s.res_pre || s.triple_out || s.pair_out || s.force_x3t || s.text_kv || s.dyn_ldc || s.f32_stream)
+    plan_bad = true;                                           // sdn_gemm_ln_* has neither a statistics output nor any of the others
+  const int64_t rows = s.M; const int N = s.N, K = s.K;
+  const std::vector<Ref> f = ln_fold_regions(wname, s.w, gamma, beta, s.bias, N, K);
   Act st;
-  if (prepass) {
-    st = act(rows, 2, 0, 0, 4);
-    Op o; o.kind = OP_ROWSTATS; o.a = R(x); o.rows = rows; o.c1 = K; o.eps = 1e-5f; o.out = R(st);
-    o.bytes = 2.0 * rows * K; snprintf(o.label, sizeof(o.label), "k_row_stats"); plan->ops.push_back(o);
-  }
+  if (prepass) { st = act(rows, 2, 0, 0, 4); row_stats(s.a, rows, K, st); }
   Op o; o.kind = OP_GEMM; memset(&o.gd, 0, sizeof(o.gd));
-  o.gd.M = (int)rows; o.gd.N = N; o.gd.K = K; o.gd.a_mode = SDN_A_PLAIN; o.gd.act = act_; o.gd.out_kind = SDN_OUT_BF16;
-  o.a = R(x); o.w = wf; o.out = out; o.ln = 1; o.ln_c = c; o.ln_d = d; o.eps = 1e-5f;
+  o.gd.M = (int)rows; o.gd.N = N; o.gd.K = K; o.gd.a_mode = SDN_A_PLAIN; o.gd.act = s.act; o.gd.out_kind = SDN_OUT_BF16;
+  o.a = s.a; o.w = f[0]; o.out = s.out; o.ln = 1; o.ln_c = f[1]; o.ln_d = f[2]; o.eps = 1e-5f;
   if (prepass) o.ln_stats = R(st);
   o.flops = 2.0 * (double)rows * N * K;
-  o.bytes = 2.0 * ((double)rows * K + (double)N * K + (double)rows * (act_ == SDN_ACT_GEGLU ? N / 2 : N));
-  { int t = sdn_gemm_pick_tile((int)rows, N, K, act_);
+  o.bytes = 2.0 * ((double)rows * K + (double)N * K + (double)rows * (s.act == SDN_ACT_GEGLU ? N / 2 : N));
+  { int t = sdn_gemm_pick_tile((int)rows, N, K, s.act);
     if (t == 8 && N % 320 == 0) t = 10;                        // (sdn_gemm_impl: the folded forms have no 256-wide instantiation)
     snprintf(o.label, sizeof(o.label), "k_gemm<%d>/ln%d", t, prepass ? 2 : 1); }   // /lnL: L = the symbol's LNF
-  if (k320_next && !prepass && K == 320 && N % 320 == 0 && act_ == SDN_ACT_NONE && pending_cols.space == SP_NONE && kK320Ln) {
+  if (s.k320 && !prepass && K == 320 && N % 320 == 0 && s.act == SDN_ACT_NONE && kK320Ln) {
     o.k320 = 1;                                                // statistics from the fragments, as LNF = 1: sdn_gemm_k320
     snprintf(o.label, sizeof(o.label), "k_gemm_k320/ln1");
   }
-  k320_next = false;
-  plan->ops.push_back(o);
-  plan->flops += o.flops;
+  emit(o);
   if (prepass) drop(st);
 }
 
@@ -74,28 +81,20 @@ Act Builder::resnet(const std::string& pfx, Act& x, Act* skip, int cout) {
   Act g1 = act(rows, cin, x.hw, x.side);
   groupnorm(x, skip, 1e-5f, 1, n1g, n1b, g1);
   Act h = act_gn(rows, cout, x.hw, x.side);
-  want_stats(h);
-  conv3x3(g1, cout, cout, c1w, c1b, R(h), 1, 0, Ref(), Ref{SP_WS, tproj.off + (int64_t)tcol * 4}, u->tproj_total);
+  conv3x3(ConvSpec(g1, cout, c1w, c1b, R(h)).with_rowbias(Ref{SP_WS, tproj.off + (int64_t)tcol * 4}, u->tproj_total).with_cols(stats_of(h)));
   drop(g1);
   Act g2 = act(rows, cout, x.hw, x.side);
   groupnorm(h, nullptr, 1e-5f, 1, n2g, n2b, g2);
   drop(h);
   Act out = act_gn(rows, cout, x.hw, x.side);
+  Act sc;                                                    // the shortcut: x itself, or its 1x1 conv
   if (cin != cout) {
     Ref scw = param(pfx + ".conv_shortcut.weight", SDN_P_MAT, cout, cin), scb = param(pfx + ".conv_shortcut.bias", SDN_P_VEC_F32, cout, 0);
-    Act sc = act(rows, cout, x.hw, x.side);
-    gemm(rows, cout, cin, R(x), scw, scb, R(sc), SDN_ACT_NONE, Ref(), SDN_OUT_BF16, 0, skip ? R(*skip) : Ref(),
-         skip ? x.C : 0);
-    want_stats(out);
-    res_pre_next = u->res_pre;
-    conv3x3(g2, cout, cout, c2w, c2b, R(out), 1, 0, R(sc), Ref(), 0);
-    drop(sc);
-  } else {
-    want_stats(out);
-    res_pre_next = u->res_pre;
-    conv3x3(g2, cout, cout, c2w, c2b, R(out), 1, 0, R(x), Ref(), 0);
+    sc = act(rows, cout, x.hw, x.side);
+    gemm(GemmSpec(rows, cout, cin, R(x), scw, scb, R(sc)).with_a2(skip ? R(*skip) : Ref(), skip ? x.C : 0));
   }
-  drop(g2);
+  conv3x3(ConvSpec(g2, cout, c2w, c2b, R(out)).with_residual(cin != cout ? R(sc) : R(x)).with_res_pre(u->res_pre).with_cols(stats_of(out)));
+  drop(sc); drop(g2);
   return out;
 }
 
@@ -149,47 +148,37 @@ void Builder::transformer_body(const std::string& pfx, Act& x, const Act& out, i
   // the five K = 320 linears of a C = 320 block (16-bit plans, whole batch) run on k_gemm_k320: proj_in, qkv,
   // attn1.to_out, attn2.to_q, attn2.to_out -- same bits as the k_gemm_dma launches they replace
   const bool k320 = u->gemm_k320 && C == 320 && es == 2 && !x3t && u->subbatch_bytes == 0;
-  k320_next = k320;
-  gemm(rows, C, C, R(gn), piw, pib, R(h));
+  gemm(GemmSpec(rows, C, C, R(gn), piw, pib, R(h)).with_k320(k320));
   drop(gn);
   // LayerNorm folding (gemm_ln): measured per shape (tools/bench_lnfold.py) -- it pays at C = 320 / 640 for the
   // attention projections (statistics inside the kernel while N <= 960, from a read-only pre-pass above) and at
   // C = 320 for the GEGLU projection; the wide, MFMA-bound projections of the lower levels keep the LayerNorm kernel.
   const bool fold12 = u->ln_fold && C <= 640, fold3 = u->ln_fold && C == 320;
-  const int hdx = C / u->cfg.n_heads;
-  const bool x3p_cross = x3t && u->x3_pairs && u->subbatch_bytes == 0 && (hdx == 40 || hdx == 80 || hdx == 160);   // sdn_attention_x3_pairs on the cross-attention too
-  // self-attention
+  const int hd = C / u->cfg.n_heads;
+  const bool x3p = x3t && u->x3_pairs && (hd == 40 || hd == 80 || hd == 160);     // head sizes of sdn_attention_x3_pairs
+  const bool x3p_self = x3p && (int64_t)hw * 6 * C * 2 < (1LL << 31), x3p_cross = x3p && u->subbatch_bytes == 0;   // ... on the cross-attention too
+  // a projection behind a LayerNorm: folded into the GEMM, or the norm's own launch into `ln` in front of it
   Act ln;
+  auto ln_gemm = [&](bool fold, const Act& in, const char* wname, Ref g, Ref b, bool prepass, GemmSpec s) {
+    if (fold) { s.a = R(in); gemm_ln(s, tb + wname, g, b, prepass); }
+    else { layernorm(in, g, b, ln); s.a = R(ln); gemm(s); }
+  };
+  // self-attention
   if (!fold12 || !fold3) ln = act(rows, C, hw, x.side);
   Act qkvb = act(rows, 3 * C, hw, x.side);
-  k320_next = k320;
-  if (fold12) {
-    gemm_ln(h, rows, 3 * C, C, tb + ".attn1.to_q.weight", qkv, l1g, l1b, Ref(), R(qkvb), SDN_ACT_NONE, 3 * C > 960 || u->ln_prepass_all);
-  } else {
-    layernorm(h, l1g, l1b, ln);
-    const int hd1 = C / u->cfg.n_heads;
-    if (x3t && u->x3_pairs && (hd1 == 40 || hd1 == 80 || hd1 == 160) && (int64_t)hw * 6 * C * 2 < (1LL << 31)) pair_out_next = true;
-    gemm(rows, 3 * C, C, R(ln), qkv, Ref(), R(qkvb));
-  }
+  ln_gemm(fold12, h, ".attn1.to_q.weight", l1g, l1b, 3 * C > 960 || u->ln_prepass_all,
+          GemmSpec(rows, 3 * C, C, Ref(), qkv, Ref(), R(qkvb)).with_k320(k320).with_pair_out(!fold12 && x3p_self));
   Act at = act(rows, C, hw, x.side);
   attention(R(qkvb), Ref{SP_WS, qkvb.off + (int64_t)C * es}, Ref{SP_WS, qkvb.off + (int64_t)2 * C * es}, R(at), hw, hw, C,
             3 * C, 3 * C, 3 * C);
   drop(qkvb);
   Act h2 = act(rows, C, hw, x.side);
-  res_pre_next = u->res_pre;
-  k320_next = k320;
-  gemm(rows, C, C, R(at), o1w, o1b, R(h2), SDN_ACT_NONE, R(h));
+  gemm(GemmSpec(rows, C, C, R(at), o1w, o1b, R(h2)).with_residual(R(h)).with_res_pre(u->res_pre).with_k320(k320));
   drop(h);
   // cross-attention
   Act qb = act(rows, C, hw, x.side);
-  k320_next = k320;
-  if (fold12) {
-    gemm_ln(h2, rows, C, C, tb + ".attn2.to_q.weight", q2w, l2g, l2b, Ref(), R(qb), SDN_ACT_NONE, u->ln_prepass_all != 0);
-  } else {
-    layernorm(h2, l2g, l2b, ln);
-    if (x3p_cross) pair_out_next = true;
-    gemm(rows, C, C, R(ln), q2w, Ref(), R(qb));
-  }
+  ln_gemm(fold12, h2, ".attn2.to_q.weight", l2g, l2b, u->ln_prepass_all != 0,
+          GemmSpec(rows, C, C, Ref(), q2w, Ref(), R(qb)).with_k320(k320).with_pair_out(!fold12 && x3p_cross));
   if (rep > 1) {                                 // from here on the branches differ (their text does)
     if (ln.off >= 0) drop(ln);
     drop(at);
@@ -205,86 +194,67 @@ void Builder::transformer_body(const std::string& pfx, Act& x, const Act& out, i
   }
   if (u->subbatch_bytes > 0) {
     Act kvb = act((int64_t)B * T, 2 * C);
-    gemm((int64_t)B * T, 2 * C, X, Ref{SP_TEXT, text_off}, kv2, Ref(), R(kvb));
+    gemm(GemmSpec((int64_t)B * T, 2 * C, X, Ref{SP_TEXT, text_off}, kv2, Ref(), R(kvb)));
     attention(R(qb), R(kvb), Ref{SP_WS, kvb.off + (int64_t)C * es}, R(at), hw, T, C, C, 2 * C, 2 * C);
     drop(qb); drop(kvb);
   } else {
     // the text's keys / values live in the workspace's persistent tail: no other op ever writes there, so a forward that is
-    // handed the same text version can skip this projection and read the previous forward's output (sdn_unet::text_version)
+    // handed the same text version can skip this projection and read the previous forward's output (sdn_unet::text_version).
+    // x3p_cross: text K / V as pair rows [hi(2C) | lo(2C)] (same bytes as f32)
     const Ref kvr{SP_KV, kv_top};
     kv_top += Arena::up((int64_t)B * T * 2 * C * es);
-    if (x3p_cross) { force_x3t_next = true; pair_out_next = true; }       // text K / V as pair rows [hi(2C) | lo(2C)] (same bytes as f32)
-    gemm((int64_t)B * T, 2 * C, X, Ref{SP_TEXT, text_off}, kv2, Ref(), kvr);
-    plan->ops.back().text_kv = 1;
+    gemm(GemmSpec((int64_t)B * T, 2 * C, X, Ref{SP_TEXT, text_off}, kv2, Ref(), kvr).with_text_kv().with_force_x3t(x3p_cross).with_pair_out(x3p_cross));
     attention(R(qb), kvr, Ref{SP_KV, kvr.off + (int64_t)C * es}, R(at), hw, T, C, C, 2 * C, 2 * C, x3p_cross);
     drop(qb);
   }
   Act h3 = act(rows, C, hw, x.side);
-  res_pre_next = u->res_pre;
-  k320_next = k320;
-  gemm(rows, C, C, R(at), o2w, o2b, R(h3), SDN_ACT_NONE, R(h2));
+  gemm(GemmSpec(rows, C, C, R(at), o2w, o2b, R(h3)).with_residual(R(h2)).with_res_pre(u->res_pre).with_k320(k320));
   drop(h2); drop(at);
   // GEGLU feed-forward
+  const Ref xres = R(rep > 1 ? *x_full : x);     // the block's residual
+  // out = x + Wpo (h3 + W2 ff + b2) + bpo = x + [ff | h3] . [Wpo W2 | Wpo]^T + (Wpo b2 + bpo): the FeedForward output linear and
+  // proj_out as one contraction over K = 5C, with the product weight / bias {wcat, bcat} derived once per weight set
+  auto ff_pair = [&] {
+    return derived_job({{pfx + ".proj_out.weight#ff", (int64_t)C * 5 * C * 2}, {pfx + ".proj_out.bias#ff", (int64_t)C * 4}},
+                       {f2w.off, pow_.off, f2b.off, pob.off, -1, -1, -1, C, 4 * C, 1});
+  };
   if (fold3 && u->ff_fuse && u->ffn_fuse && C == 320) {
     // norm3 -> GEGLU projection -> [ff | h3] . [Wpo W2 | Wpo]^T + residual as ONE launch (sdn_ffn.hip): the [rows, 4C] hidden
     // activation stays in LDS.  Same derived weights as the two launches below, same bits.
     if (ln.off >= 0) drop(ln);
-    const std::string wname = tb + ".ff.net.0.proj.weight";
-    const bool fresh1 = u->param_index.find(wname + "#ln") == u->param_index.end();
-    Ref wf = derived(wname + "#ln", (int64_t)8 * C * C * 2), c1 = derived(wname + "#ln_c", (int64_t)8 * C * 4), d1 = derived(wname + "#ln_d", (int64_t)8 * C * 4);
-    if (fresh1) u->fold_jobs.push_back({f1w.off, l3g.off, l3b.off, f1b.off, wf.off, c1.off, d1.off, 8 * C, C});
-    const bool fresh2 = u->param_index.find(pfx + ".proj_out.weight#ff") == u->param_index.end();
-    Ref wcat = derived(pfx + ".proj_out.weight#ff", (int64_t)C * 5 * C * 2), bcat = derived(pfx + ".proj_out.bias#ff", (int64_t)C * 4);
-    if (fresh2) { sdn_unet::FoldJob j{f2w.off, pow_.off, f2b.off, pob.off, wcat.off, bcat.off, -1, C, 4 * C}; j.kind = 1; u->fold_jobs.push_back(j); }
+    const std::vector<Ref> f1 = ln_fold_regions(tb + ".ff.net.0.proj.weight", f1w, l3g, l3b, f1b, 8 * C, C), f2 = ff_pair();
     // norm3's row statistics: from the operand fragments inside k_ffn320 (ffn_own_stats), or by a read-only pre-pass over h3
     Act st;
-    if (!u->ffn_own_stats) {
-      st = act(rows, 2, 0, 0, 4);
-      Op o; o.kind = OP_ROWSTATS; o.a = R(h3); o.rows = rows; o.c1 = C; o.eps = 1e-5f; o.out = R(st);
-      o.bytes = 2.0 * rows * C; snprintf(o.label, sizeof(o.label), "k_row_stats"); plan->ops.push_back(o);
-    }
-    want_stats(out);
-    Op o; o.kind = OP_FFN; o.a = R(h3); if (st.off >= 0) o.ln_stats = R(st); o.w = wf; o.ln_c = c1; o.ln_d = d1; o.a2 = wcat; o.bias = bcat;
-    o.residual = R(rep > 1 ? *x_full : x); o.out = R(out); o.rows = rows; o.c1 = C;
-    o.col = pending_cols; pending_cols = Ref();
+    if (!u->ffn_own_stats) { st = act(rows, 2, 0, 0, 4); row_stats(R(h3), rows, C, st); }
+    Op o; o.kind = OP_FFN; o.a = R(h3); if (st.off >= 0) o.ln_stats = R(st); o.w = f1[0]; o.ln_c = f1[1]; o.ln_d = f1[2]; o.a2 = f2[0]; o.bias = f2[1];
+    o.residual = xres; o.out = R(out); o.rows = rows; o.c1 = C;
+    o.col = stats_of(out);
     o.flops = 2.0 * (double)rows * ((double)8 * C * C + (double)C * 5 * C);
     o.bytes = 2.0 * ((double)rows * C * 3 + (double)8 * C * C + (double)5 * C * C);
     snprintf(o.label, sizeof(o.label), "k_ffn320");
-    plan->ops.push_back(o);
-    plan->flops += o.flops;
+    emit(o);
     if (st.off >= 0) drop(st);
     drop(h3);
     return;
   }
   Act ff = act(rows, 4 * C, hw, x.side);
-  if (fold3) {
-    // (the two-launch form of the C = 320 feed-forward is the fallback / equality partner of k_ffn320: it takes its statistics
-    //  the way that kernel does -- from the fragments when ffn_own_stats, else from the pre-pass)
-    gemm_ln(h3, rows, 8 * C, C, tb + ".ff.net.0.proj.weight", f1w, l3g, l3b, f1b, R(ff), SDN_ACT_GEGLU, !u->ffn_own_stats);
-  } else {
-    layernorm(h3, l3g, l3b, ln);
-    gemm(rows, 8 * C, C, R(ln), f1w, f1b, R(ff), SDN_ACT_GEGLU);
-  }
+  // (fold3: the two-launch form of the C = 320 feed-forward is the fallback / equality partner of k_ffn320: it takes its statistics
+  //  the way that kernel does -- from the fragments when ffn_own_stats, else from the pre-pass)
+  ln_gemm(fold3, h3, ".ff.net.0.proj.weight", l3g, l3b, !u->ffn_own_stats, GemmSpec(rows, 8 * C, C, Ref(), f1w, f1b, R(ff)).with_act(SDN_ACT_GEGLU));
   if (ln.off >= 0) drop(ln);
   if (u->ff_fuse) {
-    // out = x + Wpo (h3 + W2 ff + b2) + bpo = x + [ff | h3] . [Wpo W2 | Wpo]^T + (Wpo b2 + bpo): the FeedForward output linear
-    // and proj_out are one GEMM (two-source A operand, K = 5C); the [M, C] tensor between them is never written or re-read
-    // and the worst-shaped launch of the block (M x C x C) disappears.  The product weight is derived once per weight set.
-    const bool fresh = u->param_index.find(pfx + ".proj_out.weight#ff") == u->param_index.end();
-    Ref wcat = derived(pfx + ".proj_out.weight#ff", (int64_t)C * 5 * C * 2), bcat = derived(pfx + ".proj_out.bias#ff", (int64_t)C * 4);
-    if (fresh) { sdn_unet::FoldJob j{f2w.off, pow_.off, f2b.off, pob.off, wcat.off, bcat.off, -1, C, 4 * C}; j.kind = 1; u->fold_jobs.push_back(j); }
-    want_stats(out);
-    res_pre_next = u->res_pre && C != 320;       // (C = 320 must keep the bits of the one-launch k_ffn320, which adds it in its epilogue)
-    gemm(rows, C, 5 * C, R(ff), wcat, bcat, R(out), SDN_ACT_NONE, R(rep > 1 ? *x_full : x), SDN_OUT_BF16, 0, R(h3), 4 * C);
+    // two-source A operand: the [M, C] tensor between the two linears is never written or re-read and the worst-shaped launch
+    // of the block (M x C x C) disappears.  (C = 320 must keep the bits of the one-launch k_ffn320, which adds x in its epilogue)
+    const std::vector<Ref> f2 = ff_pair();
+    gemm(GemmSpec(rows, C, 5 * C, R(ff), f2[0], f2[1], R(out)).with_a2(R(h3), 4 * C).with_residual(xres).with_res_pre(u->res_pre && C != 320)
+             .with_cols(stats_of(out)));
     drop(ff); drop(h3);
     return;
   }
   Act h4 = act(rows, C, hw, x.side);
-  triple_out_next = x3t;                                  // (bf16x3 plan: proj_out is its only reader)
-  gemm(rows, C, 4 * C, R(ff), f2w, f2b, R(h4), SDN_ACT_NONE, R(h3));
+  gemm(GemmSpec(rows, C, 4 * C, R(ff), f2w, f2b, R(h4)).with_residual(R(h3)).with_triple_out(x3t));   // (bf16x3 plan: proj_out is its only reader)
   drop(ff); drop(h3);
-  want_stats(out);
-  gemm(rows, C, C, R(h4), pow_, pob, R(out), SDN_ACT_NONE, R(rep > 1 ? *x_full : x));
+  gemm(GemmSpec(rows, C, C, R(h4), pow_, pob, R(out)).with_residual(xres).with_cols(stats_of(out)));
   drop(h4);
 }
 
@@ -319,37 +289,24 @@ void Builder::build() {
   Ref l2w = param("time_embedding.linear_2.weight", SDN_P_MAT, tdim, tdim), l2b = param("time_embedding.linear_2.bias", SDN_P_VEC_F32, tdim, 0);
   const std::vector<Res> rs = enumerate_resnets();
   int total = 0;
-  Ref tpw, tpb;
-  {
-    int64_t expect = -1;
-    for (size_t i = 0; i < rs.size(); ++i) {
-      Ref r = param(rs[i].pfx + ".time_emb_proj.weight", SDN_P_MAT, rs[i].cout, tdim);
-      if (i == 0) tpw = r; else if (r.off != expect) { fprintf(stderr, "libsdn: time_emb_proj not contiguous\n"); abort(); }
-      expect = r.off + (int64_t)rs[i].cout * tdim * es;
-      total += rs[i].cout;
-    }
-    expect = -1;
-    for (size_t i = 0; i < rs.size(); ++i) {
-      Ref r = param(rs[i].pfx + ".time_emb_proj.bias", SDN_P_VEC_F32, rs[i].cout, 0);
-      if (i == 0) tpb = r; else if (r.off != expect) { fprintf(stderr, "libsdn: time_emb_proj bias not contiguous\n"); abort(); }
-      expect = r.off + (int64_t)rs[i].cout * 4;
-    }
-  }
+  std::vector<std::pair<std::string, int>> tw, tb;
+  for (const Res& r : rs) { tw.push_back({r.pfx + ".time_emb_proj.weight", r.cout}); tb.push_back({r.pfx + ".time_emb_proj.bias", r.cout}); total += r.cout; }
+  Ref tpw = stacked(tw, tdim), tpb = stacked(tb, 0);
   u->tproj_total = total;
   gn_stats = Ref{SP_WS, arena.alloc((int64_t)B * 129 * 64 * 2 * 4)};
   plan->tscalar_off = arena.alloc(256);
   Act tsin = act(B, ch0);
-  { Op o; o.kind = OP_TEMB; o.batch = B; o.c1 = ch0; o.out = R(tsin); snprintf(o.label, sizeof(o.label), "k_temb"); plan->ops.push_back(o); }
+  { Op o; o.kind = OP_TEMB; o.batch = B; o.c1 = ch0; o.out = R(tsin); snprintf(o.label, sizeof(o.label), "k_temb"); emit(o); }
   x3t_hold = true;                                            // M = batch: the per-sample time-embedding linears
   Act t1 = act(B, tdim);
-  gemm(B, tdim, ch0, R(tsin), l1w, l1b, R(t1), SDN_ACT_SILU);
+  gemm(GemmSpec(B, tdim, ch0, R(tsin), l1w, l1b, R(t1)).with_act(SDN_ACT_SILU));
   drop(tsin);
   Act semb = act(B, tdim);
-  gemm(B, tdim, tdim, R(t1), l2w, l2b, R(semb), SDN_ACT_SILU);
+  gemm(GemmSpec(B, tdim, tdim, R(t1), l2w, l2b, R(semb)).with_act(SDN_ACT_SILU));
   drop(t1);
   Act tp = act(B, total, 0, 0, 4);
   tproj = R(tp);
-  gemm(B, total, tdim, R(semb), tpw, tpb, R(tp), SDN_ACT_NONE, Ref(), SDN_OUT_F32);
+  gemm(GemmSpec(B, total, tdim, R(semb), tpw, tpb, R(tp)).with_out_kind(SDN_OUT_F32));
   drop(semb);
   x3t_hold = false;
 
@@ -363,8 +320,7 @@ void Builder::build() {
   Act hp = act((int64_t)Bp * S * S, ch0, S * S, S);
   { Op o; o.kind = OP_CONV_IN; o.batch = Bp; o.c1 = c.in_channels; o.c2 = ch0; o.hw = S; o.a = Ref{SP_IN, 0}; o.w = ciw; o.bias = cib; o.out = R(hp);
     o.flops = 2.0 * Bp * S * S * (double)ch0 * 9 * c.in_channels; o.bytes = (double)Bp * S * S * (4.0 * c.in_channels + 2.0 * ch0);
-    snprintf(o.label, sizeof(o.label), "k_conv_in"); plan->ops.push_back(o);
-    plan->flops += o.flops; }
+    snprintf(o.label, sizeof(o.label), "k_conv_in"); emit(o); }
   Act h = hp;
   if (rep > 1) { h = act((int64_t)B * S * S, ch0, S * S, S); repeat(hp, h, rep); }
 
@@ -408,8 +364,7 @@ void Builder::build() {
       Ref w = param(std::string(buf) + ".weight", SDN_P_CONV3X3, cout, 9 * cout), bb = param(std::string(buf) + ".bias", SDN_P_VEC_F32, cout, 0);
       const int s2 = cur.side / 2;
       Act d = act_gn((int64_t)B * s2 * s2, cout, s2 * s2, s2);
-      want_stats(d);
-      conv3x3(cur, cout, cout, w, bb, R(d), 2, 0, Ref(), Ref(), 0);
+      conv3x3(ConvSpec(cur, cout, w, bb, R(d)).with_stride(2).with_cols(stats_of(d)));
       cur = d; skips.push_back(cur); cur_is_skip = true;
     }
   }
@@ -442,8 +397,7 @@ void Builder::build() {
       Ref w = param(std::string(buf) + ".weight", SDN_P_CONV3X3, cout, 9 * cout), bb = param(std::string(buf) + ".bias", SDN_P_VEC_F32, cout, 0);
       const int s2 = cur.side * 2;
       Act up = act_gn((int64_t)B * s2 * s2, cout, s2 * s2, s2);
-      want_stats(up);
-      conv3x3(cur, cout, cout, w, bb, R(up), 1, 1, Ref(), Ref(), 0);
+      conv3x3(ConvSpec(cur, cout, w, bb, R(up)).with_upsample().with_cols(stats_of(up)));
       drop(cur); cur = up;
     }
   }
@@ -455,11 +409,11 @@ void Builder::build() {
   Act g = act((int64_t)B * S * S, ch0, S * S, S);
   groupnorm(cur, nullptr, 1e-5f, 1, og, ob, g);
   drop(cur);
-  conv3x3(g, c.out_channels, npad, cow, cob, Ref{SP_OUT, 0}, 1, 0, Ref(), Ref(), 0, SDN_OUT_F32_NCHW, c.out_channels);
+  conv3x3(ConvSpec(g, c.out_channels, cow, cob, Ref{SP_OUT, 0}).with_nchw_out(npad));
   drop(g);
   finish_up4();
   plan->kv_base = Arena::up(arena.peak);
-  plan->ws_bytes = plan_bad ? -1 : plan->kv_base + kv_top;
+  plan->ws_bytes = plan->kv_base + kv_top;
 }
 
 }  // namespace sdn_plan

@@ -23,25 +23,20 @@ Act Builder::vae_resnet(const std::string& pfx, Act& x, int cout) {
   Act g1 = act(rows, cin, x.hw, x.side);
   groupnorm(x, nullptr, 1e-6f, 1, n1g, n1b, g1);
   Act h = act_gn(rows, cout, x.hw, x.side);
-  want_stats(h);
-  conv3x3(g1, cout, cout, c1w, c1b, R(h), 1, 0, Ref(), Ref(), 0);
+  conv3x3(ConvSpec(g1, cout, c1w, c1b, R(h)).with_cols(stats_of(h)));
   drop(g1);
   Act g2 = act(rows, cout, x.hw, x.side);
   groupnorm(h, nullptr, 1e-6f, 1, n2g, n2b, g2);
   drop(h);
   Act out = act_gn(rows, cout, x.hw, x.side);
+  Act sc;                                                    // the shortcut: x itself, or its 1x1 conv
   if (cin != cout) {
     Ref scw = param(pfx + ".conv_shortcut.weight", SDN_P_MAT, cout, cin), scb = param(pfx + ".conv_shortcut.bias", SDN_P_VEC_F32, cout, 0);
-    Act sc = act(rows, cout, x.hw, x.side);
-    gemm(rows, cout, cin, R(x), scw, scb, R(sc));
-    want_stats(out);
-    conv3x3(g2, cout, cout, c2w, c2b, R(out), 1, 0, R(sc), Ref(), 0);
-    drop(sc);
-  } else {
-    want_stats(out);
-    conv3x3(g2, cout, cout, c2w, c2b, R(out), 1, 0, R(x), Ref(), 0);
+    sc = act(rows, cout, x.hw, x.side);
+    gemm(GemmSpec(rows, cout, cin, R(x), scw, scb, R(sc)));
   }
-  drop(g2);
+  conv3x3(ConvSpec(g2, cout, c2w, c2b, R(out)).with_residual(cin != cout ? R(sc) : R(x)).with_cols(stats_of(out)));
+  drop(sc); drop(g2);
   return out;
 }
 
@@ -59,9 +54,9 @@ Act Builder::vae_attention(const std::string& pfx, Act& x) {
   groupnorm(x, nullptr, 1e-6f, 0, gg, gb, gn);
   // three dense projections (not one stacked GEMM): the per-image Q K^T / P V GEMMs below take dense operands
   Act q = act(rows, C, hw, x.side), k = act(rows, C, hw, x.side), v = act(rows, C, hw, x.side);
-  gemm(rows, C, C, R(gn), qw, qb, R(q));
-  gemm(rows, C, C, R(gn), kw, kb, R(k));
-  gemm(rows, C, C, R(gn), vw, vb, R(v));
+  gemm(GemmSpec(rows, C, C, R(gn), qw, qb, R(q)));
+  gemm(GemmSpec(rows, C, C, R(gn), kw, kb, R(k)));
+  gemm(GemmSpec(rows, C, C, R(gn), vw, vb, R(v)));
   drop(gn);
   Act at = act(rows, C, hw, x.side);
   // fp32 scores of ONE image -- of one block of at most 4096 queries when the image has more tokens (1024 x 1024:
@@ -74,7 +69,7 @@ Act Builder::vae_attention(const std::string& pfx, Act& x) {
   for (int b = 0; b < B; ++b) {
     const int64_t img = (int64_t)b * hw * C * es;
     { Op o; o.kind = OP_TRANSPOSE; o.a = Ref{SP_WS, v.off + img}; o.out = R(vt); o.rows = hw; o.c1 = C; o.ldq = C;
-      o.ldo = hw; o.bytes = 4.0 * hw * C; snprintf(o.label, sizeof(o.label), "k_transpose16"); plan->ops.push_back(o); }
+      o.ldo = hw; o.bytes = 4.0 * hw * C; snprintf(o.label, sizeof(o.label), "k_transpose16"); emit(o); }
     for (int r0 = 0; r0 < hw; r0 += qrows) {
       const int64_t rowoff = (int64_t)r0 * C * es;
       { // S = Q K^T : A = this block's Q rows, "weight" operand = the image's K rows
@@ -83,24 +78,23 @@ Act Builder::vae_attention(const std::string& pfx, Act& x) {
         o.a = Ref{SP_WS, q.off + img + rowoff}; o.w = Ref{SP_WS, k.off + img}; o.out = R(sc);
         o.flops = 2.0 * qrows * (double)hw * C; o.bytes = 2.0 * (qrows + (double)hw) * C + 4.0 * qrows * (double)hw;
         snprintf(o.label, sizeof(o.label), "k_gemm<%d>", sdn_gemm_pick_tile(qrows, hw, C, SDN_ACT_NONE));
-        plan->ops.push_back(o); plan->flops += o.flops; plan->attn_flops += o.flops;
+        emit(o, /*attn=*/true);
       }
       { Op o; o.kind = OP_SOFTMAX; o.a = R(sc); o.out = R(pr); o.rows = qrows; o.c1 = hw; o.scale = scale;
-        o.bytes = 6.0 * qrows * (double)hw; snprintf(o.label, sizeof(o.label), "k_softmax_rows"); plan->ops.push_back(o); }
+        o.bytes = 6.0 * qrows * (double)hw; snprintf(o.label, sizeof(o.label), "k_softmax_rows"); emit(o); }
       { // O = P V : A = P [qrows, hw], "weight" = V^T [C, hw]
         Op o; o.kind = OP_GEMM; memset(&o.gd, 0, sizeof(o.gd));
         o.gd.M = qrows; o.gd.N = C; o.gd.K = hw; o.gd.a_mode = SDN_A_PLAIN; o.gd.out_kind = SDN_OUT_BF16;
         o.a = R(pr); o.w = R(vt); o.out = Ref{SP_WS, at.off + img + rowoff};
         o.flops = 2.0 * qrows * (double)hw * C; o.bytes = 2.0 * (qrows * (double)hw + (qrows + (double)hw) * C);
         snprintf(o.label, sizeof(o.label), "k_gemm<%d>", sdn_gemm_pick_tile(qrows, C, hw, SDN_ACT_NONE));
-        plan->ops.push_back(o); plan->flops += o.flops; plan->attn_flops += o.flops;
+        emit(o, /*attn=*/true);
       }
     }
   }
   drop(sc); drop(pr); drop(vt); drop(q); drop(k); drop(v);
   Act out = act_gn(rows, C, hw, x.side);
-  want_stats(out);
-  gemm(rows, C, C, R(at), ow, ob, R(out), SDN_ACT_NONE, R(x));
+  gemm(GemmSpec(rows, C, C, R(at), ow, ob, R(out)).with_residual(R(x)).with_cols(stats_of(out)));
   drop(at);
   return out;
 }
@@ -140,13 +134,12 @@ void Builder::build_vae() {
   Ref pqw = param("post_quant_conv.weight", SDN_P_VEC_F32, L * L, 0), pqb = param("post_quant_conv.bias", SDN_P_VEC_F32, L, 0);
   Act z = act((int64_t)B * L, S * S, 0, 0, 4);                    // fp32 NCHW
   { Op o; o.kind = OP_LATENT_MIX; o.batch = B; o.c1 = L; o.hw = S * S; o.a = Ref{SP_IN, 0}; o.w = pqw; o.bias = pqb; o.out = R(z);
-    o.flops = 2.0 * B * S * S * (double)L * L; o.bytes = 8.0 * B * S * S * L; snprintf(o.label, sizeof(o.label), "k_latent_mix");
-    plan->ops.push_back(o); plan->flops += o.flops; }
+    o.flops = 2.0 * B * S * S * (double)L * L; o.bytes = 8.0 * B * S * S * L; snprintf(o.label, sizeof(o.label), "k_latent_mix"); emit(o); }
   Ref ciw = param("decoder.conv_in.weight", SDN_P_CONV3X3, ctop, 9 * L), cib = param("decoder.conv_in.bias", SDN_P_VEC_F32, ctop, 0);
   Act cur = act((int64_t)B * S * S, ctop, S * S, S);
   { Op o; o.kind = OP_CONV_IN; o.batch = B; o.c1 = L; o.c2 = ctop; o.hw = S; o.a = R(z); o.w = ciw; o.bias = cib; o.out = R(cur);
     o.flops = 2.0 * B * S * S * (double)ctop * 9 * L; o.bytes = (double)B * S * S * (4.0 * L + 2.0 * ctop);
-    snprintf(o.label, sizeof(o.label), "k_conv_in"); plan->ops.push_back(o); plan->flops += o.flops; }
+    snprintf(o.label, sizeof(o.label), "k_conv_in"); emit(o); }
   drop(z);
   { Act r = vae_resnet("decoder.mid_block.resnets.0", cur, ctop); drop(cur); cur = r; }
   { Act r = vae_attention("decoder.mid_block.attentions.0", cur); drop(cur); cur = r; }
@@ -163,8 +156,7 @@ void Builder::build_vae() {
       Ref w = param(std::string(buf) + ".weight", SDN_P_CONV3X3, cout, 9 * cout), bb = param(std::string(buf) + ".bias", SDN_P_VEC_F32, cout, 0);
       const int s2 = cur.side * 2;
       Act up = act_gn((int64_t)B * s2 * s2, cout, s2 * s2, s2);
-      want_stats(up);
-      conv3x3(cur, cout, cout, w, bb, R(up), 1, 1, Ref(), Ref(), 0);
+      conv3x3(ConvSpec(cur, cout, w, bb, R(up)).with_upsample().with_cols(stats_of(up)));
       drop(cur); cur = up;
     }
   }
@@ -176,7 +168,7 @@ void Builder::build_vae() {
   Act g = act((int64_t)B * cur.hw, c0, cur.hw, cur.side);
   groupnorm(cur, nullptr, 1e-6f, 1, og, ob, g);
   drop(cur);
-  conv3x3(g, c.out_channels, npad, cow, cob, Ref{SP_OUT, 0}, 1, 0, Ref(), Ref(), 0, SDN_OUT_F32_NCHW, c.out_channels);
+  conv3x3(ConvSpec(g, c.out_channels, cow, cob, Ref{SP_OUT, 0}).with_nchw_out(npad));
   drop(g);
   if (es == 4) vae_f32_rows();
   plan->ws_bytes = arena.peak;
@@ -196,7 +188,7 @@ void Builder::build_vae_encoder() {
   Act cur = act((int64_t)B * S0 * S0, c0, S0 * S0, S0);
   { Op o; o.kind = OP_CONV_IN; o.batch = B; o.c1 = c.out_channels; o.c2 = c0; o.hw = S0; o.a = Ref{SP_IN, 0}; o.w = ciw; o.bias = cib; o.out = R(cur);
     o.flops = 2.0 * B * S0 * S0 * (double)c0 * 9 * c.out_channels; o.bytes = (double)B * S0 * S0 * (4.0 * c.out_channels + 2.0 * c0);
-    snprintf(o.label, sizeof(o.label), "k_conv_in"); plan->ops.push_back(o); plan->flops += o.flops; }
+    snprintf(o.label, sizeof(o.label), "k_conv_in"); emit(o); }
   for (int i = 0; i < n; ++i) {
     const int cout = c.block_out_channels[i];
     for (int j = 0; j < c.layers_per_block; ++j) {
@@ -209,8 +201,7 @@ void Builder::build_vae_encoder() {
       Ref w = param(std::string(buf) + ".weight", SDN_P_CONV3X3, cout, 9 * cout), bb = param(std::string(buf) + ".bias", SDN_P_VEC_F32, cout, 0);
       const int s2 = cur.side / 2;
       Act d = act_gn((int64_t)B * s2 * s2, cout, s2 * s2, s2);
-      want_stats(d);
-      conv3x3(cur, cout, cout, w, bb, R(d), 2, 0, Ref(), Ref(), 0, SDN_OUT_BF16, 0, 1);
+      conv3x3(ConvSpec(cur, cout, w, bb, R(d)).with_stride(2, /*asym_pad=*/1).with_cols(stats_of(d)));
       drop(cur); cur = d;
     }
   }
@@ -228,12 +219,11 @@ void Builder::build_vae_encoder() {
   const int hw = cur.hw;
   drop(cur);
   Act mom = act((int64_t)B * M2, hw, 0, 0, 4);                     // fp32 NCHW moments before quant_conv
-  conv3x3(g, M2, npad, cow, cob, R(mom), 1, 0, Ref(), Ref(), 0, SDN_OUT_F32_NCHW, M2);
+  conv3x3(ConvSpec(g, M2, cow, cob, R(mom)).with_nchw_out(npad));
   drop(g);
   { Op o; o.kind = OP_LATENT_MIX; o.batch = B; o.c1 = M2; o.hw = hw; o.a = R(mom); o.w = qw; o.bias = qb; o.out = Ref{SP_OUT, 0};
     o.mod = 1; o.scale = 1.0f;
-    o.flops = 2.0 * B * hw * (double)M2 * M2; o.bytes = 8.0 * B * hw * M2; snprintf(o.label, sizeof(o.label), "k_latent_mix");
-    plan->ops.push_back(o); plan->flops += o.flops; }
+    o.flops = 2.0 * B * hw * (double)M2 * M2; o.bytes = 8.0 * B * hw * M2; snprintf(o.label, sizeof(o.label), "k_latent_mix"); emit(o); }
   drop(mom);
   if (es == 4) vae_f32_rows();
   plan->ws_bytes = arena.peak;

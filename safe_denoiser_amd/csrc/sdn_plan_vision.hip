@@ -24,14 +24,14 @@ void Builder::build_clip_vision() {
   Act pr = act(prows, Kpad, P, 0);
   { Op o; o.kind = OP_PATCH_ROWS; o.a = Ref{SP_IN, 0}; o.out = R(pr); o.batch = B; o.hw = c.image_size; o.patch = c.patch_size;
     o.c1 = Kpad; o.rows = prows; o.bytes = 12.0 * B * c.image_size * c.image_size + 2.0 * prows * Kpad;
-    snprintf(o.label, sizeof(o.label), "k_clip_patch_rows"); plan->ops.push_back(o); }
+    snprintf(o.label, sizeof(o.label), "k_clip_patch_rows"); emit(o); }
   Act pp = act(prows, C, P, 0);
-  gemm(prows, C, Kpad, R(pr), pw, Ref(), R(pp));
+  gemm(GemmSpec(prows, C, Kpad, R(pr), pw, Ref(), R(pp)));
   drop(pr);
   Act x = act(rows, C, n, 0);
   { Op o; o.kind = OP_VISION_EMBED; o.a = R(pp); o.a2 = cls; o.aux = pos; o.w = pg; o.bias = pb; o.out = R(x); o.batch = B; o.hw = n;
     o.c1 = C; o.eps = 1e-5f; o.rows = rows; o.bytes = 2.0 * (prows + rows) * C;
-    snprintf(o.label, sizeof(o.label), "k_clip_vision_embed"); plan->ops.push_back(o); }
+    snprintf(o.label, sizeof(o.label), "k_clip_vision_embed"); emit(o); }
   drop(pp);
   char buf[96];
   for (int l = 0; l < c.num_layers; ++l) {
@@ -39,7 +39,7 @@ void Builder::build_clip_vision() {
     const std::string p = buf;
     Ref l1g = param(p + ".layer_norm1.weight", SDN_P_VEC_F32, C, 0), l1b = param(p + ".layer_norm1.bias", SDN_P_VEC_F32, C, 0);
     Ref qkvw = stacked({p + ".self_attn.q_proj.weight", p + ".self_attn.k_proj.weight", p + ".self_attn.v_proj.weight"}, C, C);
-    Ref qkvb = stacked_vec({p + ".self_attn.q_proj.bias", p + ".self_attn.k_proj.bias", p + ".self_attn.v_proj.bias"}, C);
+    Ref qkvb = stacked({p + ".self_attn.q_proj.bias", p + ".self_attn.k_proj.bias", p + ".self_attn.v_proj.bias"}, C, 0);
     Ref ow = param(p + ".self_attn.out_proj.weight", SDN_P_MAT, C, C), ob = param(p + ".self_attn.out_proj.bias", SDN_P_VEC_F32, C, 0);
     Ref l2g = param(p + ".layer_norm2.weight", SDN_P_VEC_F32, C, 0), l2b = param(p + ".layer_norm2.bias", SDN_P_VEC_F32, C, 0);
     Ref f1w = param(p + ".mlp.fc1.weight", SDN_P_MAT, I, C), f1b = param(p + ".mlp.fc1.bias", SDN_P_VEC_F32, I, 0);
@@ -47,35 +47,35 @@ void Builder::build_clip_vision() {
     Act ln = act(rows, C, n, 0);
     layernorm(x, l1g, l1b, ln);
     Act qkv = act(rows, 3 * C, n, 0);
-    gemm(rows, 3 * C, C, R(ln), qkvw, qkvb, R(qkv));
+    gemm(GemmSpec(rows, 3 * C, C, R(ln), qkvw, qkvb, R(qkv)));
     Act at = act(rows, C, n, 0);
     { Op o; o.kind = OP_ATTN; o.a = R(qkv); o.k = Ref{SP_WS, qkv.off + (int64_t)C * es}; o.v = Ref{SP_WS, qkv.off + (int64_t)2 * C * es};
       o.out = R(at); o.batch = B; o.heads = H; o.nq = n; o.nk = n; o.hd = C / H; o.ldq = o.ldk = o.ldv = 3 * C; o.ldo = C;
       o.scale = 1.0f / sqrtf((float)o.hd);
       o.flops = 4.0 * B * H * (double)n * n * o.hd; o.bytes = 2.0 * 4.0 * rows * C;
-      snprintf(o.label, sizeof(o.label), "k_attn<%d>", o.hd); plan->ops.push_back(o); plan->flops += o.flops; plan->attn_flops += o.flops; }
+      snprintf(o.label, sizeof(o.label), "k_attn<%d>", o.hd); emit(o); }
     drop(qkv);
     Act x2 = act(rows, C, n, 0);
-    gemm(rows, C, C, R(at), ow, ob, R(x2), SDN_ACT_NONE, R(x));
+    gemm(GemmSpec(rows, C, C, R(at), ow, ob, R(x2)).with_residual(R(x)));
     drop(at); drop(x);
     layernorm(x2, l2g, l2b, ln);
     Act h = act(rows, I, n, 0);
-    gemm(rows, I, C, R(ln), f1w, f1b, R(h), c.act);
+    gemm(GemmSpec(rows, I, C, R(ln), f1w, f1b, R(h)).with_act(c.act));
     drop(ln);
     x = act(rows, C, n, 0);
-    gemm(rows, C, I, R(h), f2w, f2b, R(x), SDN_ACT_NONE, R(x2));
+    gemm(GemmSpec(rows, C, I, R(h), f2w, f2b, R(x)).with_residual(R(x2)));
     drop(h); drop(x2);
   }
   // last_hidden_state: skipped by the interpreter when the caller gave no buffer
   { Op o; o.kind = OP_COPY_ROWS; o.a = R(x); o.out = Ref{SP_OUT, 0}; o.batch = B; o.hw = n; o.c1 = C;
-    o.bytes = 2.0 * es * rows * C; snprintf(o.label, sizeof(o.label), "k_copy_rows"); plan->ops.push_back(o); }
+    o.bytes = 2.0 * es * rows * C; snprintf(o.label, sizeof(o.label), "k_copy_rows"); emit(o); }
   Ref qg = param("post_layernorm.weight", SDN_P_VEC_F32, C, 0), qb = param("post_layernorm.bias", SDN_P_VEC_F32, C, 0);
   Ref vpw = param("visual_projection.weight", SDN_P_MAT, c.projection_dim, C);
   Act pooled = act(B, C, 1, 0);
   { Op o; o.kind = OP_CLASS_ROWS; o.a = R(x); o.w = qg; o.bias = qb; o.out = R(pooled); o.batch = B; o.hw = n; o.c1 = C; o.eps = 1e-5f;
-    o.rows = B; o.bytes = 2.0 * es * B * C; snprintf(o.label, sizeof(o.label), "k_clip_class_rows"); plan->ops.push_back(o); }
+    o.rows = B; o.bytes = 2.0 * es * B * C; snprintf(o.label, sizeof(o.label), "k_clip_class_rows"); emit(o); }
   drop(x);
-  gemm(B, c.projection_dim, C, R(pooled), vpw, Ref(), Ref{SP_OUT2, 0});
+  gemm(GemmSpec(B, c.projection_dim, C, R(pooled), vpw, Ref(), Ref{SP_OUT2, 0}));
   drop(pooled);
   plan->ws_bytes = arena.peak;
 }
