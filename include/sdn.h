@@ -513,6 +513,31 @@ int sdn_mmdit_forward(sdn_unet* m, const void* weights, const float* latents, fl
                       const void* pooled, float* out, int32_t batch, void* workspace, size_t workspace_bytes,
                       void* stream);
 
+/* The SD-3.5 additions to the MMDiT (diffusers >= 0.31 SD3Transformer2DModel: qk_norm = "rms_norm", dual_attention_layers).  The
+ * 12-int sdn_mmdit_config stays as it is; sdn_mmdit_create_ex takes the additions beside it.  ext NULL or all zero = sdn_mmdit_create:
+ * the same parameters, ops and workspace.
+ *   qk_norm 1: every attention normalises q and k per head (RMSNorm over head_dim, gains [head_dim], eps qk_norm_eps) between its
+ *     projections and the attention -- attn.norm_q / norm_k on the image stream, attn.norm_added_q / norm_added_k on the text stream.
+ *   dual_attention_mask bit i: block i has a second, image-only self-attention attn2 (to_q / to_k / to_v / to_out.0 with biases,
+ *     norm_q / norm_k under qk_norm) and a 9-chunk norm1.linear (SD35AdaLayerNormZeroX: ..., shift_msa2, scale_msa2, gate_msa2):
+ *     x += gate_msa2 * attn2(LN(x) (1 + scale_msa2) + shift_msa2) after the joint attention's residual.
+ * SDN_E_INVALID: qk_norm outside 0 / 1, qk_norm 1 with qk_norm_eps <= 0, a mask bit at or above num_layers, a non-zero mask with
+ * num_layers > 64, and whatever sdn_mmdit_create refuses. */
+typedef struct sdn_mmdit_ext {
+  int32_t qk_norm;               /* 0 none, 1 rms_norm                                         */
+  float qk_norm_eps;             /* 1e-6                                                       */
+  uint64_t dual_attention_mask;  /* bit i = block i has attn2; needs num_layers <= 64          */
+} sdn_mmdit_ext;
+int sdn_mmdit_create_ex(const sdn_mmdit_config* cfg_host, const sdn_mmdit_ext* ext_host, sdn_unet** out_host);
+/* Its row-wise operator: normalises IN PLACE columns [0, 2 * heads * 64) of each of `rows` rows of leading dimension ld (elements) --
+ * the [q | k | v] rows a stacked QKV projection writes, ld >= 3 * heads * 64 -- in groups of 64: x * rsqrt(mean(x^2) + eps) * w,
+ * statistics in f32, rounded once to the storage type; group g < heads takes wq [64], the others wk [64].  Columns from
+ * 2 * heads * 64 on are neither read nor written.  dtype 0 = bf16, 1 = fp16, 2 = f32 storage.  rows == 0 launches nothing.
+ * SDN_E_INVALID: a null pointer, heads <= 0, ld < 3 * heads * 64, ld not a multiple of 8 (16-bit) / 4 (f32) elements, qkv not
+ * 16-byte aligned, eps <= 0, dtype outside 0 ... 2. */
+int sdn_qk_rmsnorm(int32_t dtype, void* qkv, int64_t rows, int32_t heads, int32_t ld, const float* wq, const float* wk, float eps,
+                   void* stream);
+
 /* LayerNorm folded into the GEMM that consumes it (BasicTransformerBlock: norm1 -> to_q/k/v, norm2 -> attn2.to_q, norm3 ->
  * GEGLU proj; models/transformer_2d.py:239-359): out = LayerNorm_eps(A; gamma, beta) . W^T + bias [GEGLU], computed as
  * rstd[m] * (A . W'^T - mean[m] * c[n]) + d[n] with W' = W * gamma (per input channel, 16-bit), c[n] = sum_k W'[n,k],

@@ -57,6 +57,10 @@ class MmditConfig(C.Structure):
                                          "dtype")]
 
 
+class MmditExt(C.Structure):
+    _fields_ = [("qk_norm", C.c_int32), ("qk_norm_eps", C.c_float), ("dual_attention_mask", C.c_uint64)]
+
+
 class VaeConfig(C.Structure):
     _fields_ = [("latent_channels", C.c_int32), ("out_channels", C.c_int32), ("sample_size", C.c_int32),
                 ("n_levels", C.c_int32), ("block_out_channels", C.c_int32 * 4), ("layers_per_block", C.c_int32),
@@ -171,6 +175,8 @@ SIGNATURES = {
     "sdn_unet_forward": (C.c_int, [_vp, _vp, _vp, _f32, _vp, _vp, _i32, _vp, _sz, _vp]),
     "sdn_mmdit_create": (C.c_int, [C.POINTER(MmditConfig), C.POINTER(_vp)]),
     "sdn_mmdit_forward": (C.c_int, [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "sdn_mmdit_create_ex": (C.c_int, [C.POINTER(MmditConfig), C.POINTER(MmditExt), C.POINTER(_vp)]),
+    "sdn_qk_rmsnorm": (C.c_int, [_i32, _vp, _i64, _i32, _i32, _vp, _vp, _f32, _vp]),
     "sdn_joint_attention": (C.c_int, [_i32, _vp, _vp, _vp, _vp, C.POINTER(AttnSegment2), _i32, _i32, _i32, _i32, _i32,
                                       _i32, _i32, _i32, _f32, _vp]),
     "sdn_layernorm_mod_bf16": (C.c_int, [_vp, _i64, _i32, _f32, _vp, _vp, _i32, _i32, _vp, _vp]),

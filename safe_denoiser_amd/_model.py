@@ -45,9 +45,10 @@ class EngineModel:
         self.precision = precision or ("fp32" if dtype == torch.float32 else None)
         return 3 if self.precision == "bf16x3" else DTYPE_CODES[dtype]
 
-    def _create(self, create_fn: str, cstruct):
+    def _create(self, create_fn: str, cstruct, *more):
+        """`more`: further structs the creator takes between its config and the handle (sdn_mmdit_create_ex's sdn_mmdit_ext)."""
         h = C.c_void_p()
-        _lib.check(getattr(_lib.lib(), create_fn)(C.byref(cstruct), C.byref(h)), create_fn)
+        _lib.check(getattr(_lib.lib(), create_fn)(C.byref(cstruct), *[C.byref(s) for s in more], C.byref(h)), create_fn)
         self._h = h
         self._weights = None
         self._ws = {}

@@ -113,13 +113,23 @@ def unet_kwargs(cfg: dict) -> dict:
     return out
 
 
-def mmdit_kwargs(cfg: dict) -> dict:
-    """SD3Transformer2DModel(**kwargs) from transformer/config.json (the SD-v3 family; SD3-medium's file).  The plan has no q/k
-    RMS norm and no second attention per block (the SD-3.5 additions), and its text projection is as wide as the blocks."""
-    _require(cfg, "transformer", qk_norm=None)
-    if cfg.get("dual_attention_layers"):
-        raise NotImplementedError(f"transformer: config value dual_attention_layers = {cfg['dual_attention_layers']!r} is not "
-                                  "implemented by the engine's plan (needs ())")
+def mmdit_kwargs(cfg: dict, sd35: bool = False) -> dict:
+    """SD3Transformer2DModel(**kwargs) from transformer/config.json (the SD-v3 family; SD3-medium's file).  Without `sd35` the plan
+    has no q/k RMS norm and no second attention per block (the SD-3.5 additions); with it, qk_norm = "rms_norm" and a list of
+    dual_attention_layers are accepted and returned (SD-3.5-medium's file).  Either way the text projection is as wide as the
+    blocks, and that width is at most 2048 (SD-3.5-large is 2432 wide)."""
+    dual = cfg.get("dual_attention_layers") or ()
+    if not sd35:
+        _require(cfg, "transformer", qk_norm=None)
+        if dual:
+            raise NotImplementedError(f"transformer: config value dual_attention_layers = {cfg['dual_attention_layers']!r} is not "
+                                      "implemented by the engine's plan (needs ())")
+    else:
+        _require(cfg, "transformer", qk_norm=(None, "rms_norm"))
+        layers = cfg.get("num_layers", 24)
+        if not all(isinstance(i, int) and 0 <= i < layers for i in dual):
+            raise NotImplementedError(f"transformer: config value dual_attention_layers = {cfg['dual_attention_layers']!r} is not "
+                                      f"implemented by the engine's plan (needs block indices below num_layers = {layers})")
     arch = cfg.get("_class_name")
     if arch is not None and arch != "SD3Transformer2DModel":
         raise NotImplementedError(f"transformer: _class_name = {arch!r} is not implemented (needs 'SD3Transformer2DModel')")
@@ -129,7 +139,13 @@ def mmdit_kwargs(cfg: dict) -> dict:
                                   f"implemented by the engine's plan (needs num_attention_heads * attention_head_dim = {heads * hd})")
     keys = ("in_channels", "out_channels", "sample_size", "patch_size", "num_layers", "num_attention_heads", "attention_head_dim",
             "joint_attention_dim", "pooled_projection_dim", "pos_embed_max_size")
-    return {k: cfg[k] for k in keys if k in cfg}
+    out = {k: cfg[k] for k in keys if k in cfg}
+    if sd35:
+        if heads * hd > 2048:
+            raise NotImplementedError(f"transformer: width num_attention_heads * attention_head_dim = {heads} * {hd} = {heads * hd} is "
+                                      "not implemented by the engine's plan (needs at most 2048; SD-3.5-large is 2432 wide)")
+        out.update(qk_norm=cfg.get("qk_norm"), dual_attention_layers=tuple(dual))
+    return out
 
 
 def vae_kwargs(cfg: dict) -> dict:

@@ -53,7 +53,8 @@ enum OpKind { OP_TEMB, OP_CONV_IN, OP_GEMM, OP_GN, OP_LN, OP_ATTN, OP_PATCHIFY, 
               OP_TRANSPOSE, OP_REPEAT = 12 /* 11 is unassigned: tests/golden/plan_digests.json pins the numbers */, OP_CLIP_EMBED, OP_MATTN,
               OP_ROWSTATS, OP_FFN, OP_SPLIT3,
               OP_RMSNORM, OP_EMBED, OP_T5_BIAS, OP_BATTN, OP_EOS_ROWS, OP_COPY_ROWS, OP_PATCH_ROWS, OP_VISION_EMBED, OP_CLASS_ROWS,
-              OP_CONV_ROWS, OP_POOL3, OP_RESIZE, OP_SPATIAL_MEAN };
+              OP_CONV_ROWS, OP_POOL3, OP_RESIZE, OP_SPATIAL_MEAN,
+              OP_QK_RMSNORM /* a = the [q | k | v] rows (in place), w = wq, bias = wk, rows, heads, ldq = ld, eps */ };
 
 struct Op {
   int kind;
@@ -149,6 +150,7 @@ struct sdn_unet {
   sdn_plan::ModelKind kind = sdn_plan::UNET;   // set once by the creator
   sdn_unet_config cfg;                  // UNET; a VAE mirrors its norm_groups here (the shared GroupNorm emitter reads cfg.norm_groups)
   sdn_mmdit_config mcfg;
+  sdn_mmdit_ext mext = {0, 0.f, 0};     // MMDIT: the SD-3.5 additions (sdn_mmdit_create_ex); all zero = the SD3 plan
   sdn_vae_config vcfg;
   sdn_clip_config ccfg;
   sdn_clip_proj_config pcfg;            // CLIP_PROJ: ccfg mirrors its encoder fields (same layers as CLIP)
@@ -350,6 +352,7 @@ struct Builder {
   // ---- SD-v3 MMDiT (sdn_plan_mmdit.hip) --------------------------------------------------------------
   void gemm_ex(const GemmSpec& s);
   void ln_mod(const Act& x, int64_t rows, int rows_per_batch, Ref scale, Ref shift, int ld, const Act& out);
+  void qk_rmsnorm(const Act& qkv, int64_t rows, Ref wq, Ref wk);
   Ref fcol(int col) const { return Ref{SP_WS, tproj.off + (int64_t)col * 4}; }   // column of the stacked adaLN output
   void build_mmdit();
 

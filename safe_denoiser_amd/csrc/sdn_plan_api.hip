@@ -47,7 +47,9 @@ int sdn_unet_create(const sdn_unet_config* cfg, sdn_unet** out) {
   return SDN_OK;
 }
 
-int sdn_mmdit_create(const sdn_mmdit_config* cfg, sdn_unet** out) {
+int sdn_mmdit_create(const sdn_mmdit_config* cfg, sdn_unet** out) { return sdn_mmdit_create_ex(cfg, nullptr, out); }
+
+int sdn_mmdit_create_ex(const sdn_mmdit_config* cfg, const sdn_mmdit_ext* ext, sdn_unet** out) {
   if (!cfg || !out) return SDN_E_INVALID;
   const int C = cfg->num_heads * cfg->head_dim;
   if (cfg->in_channels <= 0 || cfg->out_channels <= 0 || cfg->sample_size <= 0 || cfg->patch_size <= 0 ||
@@ -57,9 +59,15 @@ int sdn_mmdit_create(const sdn_mmdit_config* cfg, sdn_unet** out) {
       (cfg->out_channels * cfg->patch_size * cfg->patch_size) % 32 != 0 || cfg->text_len <= 0 || cfg->dtype < 0 ||
       cfg->dtype > 3 || C > 2048)
     return SDN_E_INVALID;
+  if (ext) {                                                   // the SD-3.5 additions: NULL or all zero = the SD3 plan
+    if (ext->qk_norm < 0 || ext->qk_norm > 1 || (ext->qk_norm == 1 && !(ext->qk_norm_eps > 0.f))) return SDN_E_INVALID;
+    if (ext->dual_attention_mask && (cfg->num_layers > 64 || (cfg->num_layers < 64 && (ext->dual_attention_mask >> cfg->num_layers))))
+      return SDN_E_INVALID;
+  }
   sdn_unet* u = new sdn_unet();
   memset(&u->cfg, 0, sizeof(u->cfg));
   u->mcfg = *cfg;
+  if (ext) u->mext = *ext;
   u->kind = MMDIT;
   get_plan(u, 1);
   *out = u;

@@ -34,9 +34,19 @@ void Builder::ln_mod(const Act& x, int64_t rows, int rows_per_batch, Ref scale, 
   snprintf(o.label, sizeof(o.label), es == 4 ? "k_layernorm_mod_f32" : "k_layernorm");
   emit(o);
 }
+// SD-3.5 q/k RMS norm, in place on the q and k thirds of a stacked QKV projection's rows (sdn_qk_rmsnorm): reads and writes 2C per row
+void Builder::qk_rmsnorm(const Act& qkv, int64_t rows, Ref wq, Ref wk) {
+  Op o; o.kind = OP_QK_RMSNORM; o.a = R(qkv); o.w = wq; o.bias = wk; o.rows = rows; o.heads = u->mcfg.num_heads; o.ldq = qkv.C;
+  o.eps = u->mext.qk_norm_eps;
+  o.bytes = 2.0 * es * (double)rows * 2.0 * (o.heads * u->mcfg.head_dim);
+  snprintf(o.label, sizeof(o.label), "k_qk_rmsnorm");
+  emit(o);
+}
 
 void Builder::build_mmdit() {
   const sdn_mmdit_config& c = u->mcfg;
+  const bool qkn = u->mext.qk_norm == 1;                                         // the SD-3.5 additions (sdn_mmdit_create_ex)
+  auto dual = [&](int i) { return i < 64 && ((u->mext.dual_attention_mask >> i) & 1) != 0; };
   const int C = c.num_heads * c.head_dim, S = c.sample_size, ps = c.patch_size, hp = S / ps, N = hp * hp;
   const int T = c.text_len, L = c.num_layers, KP = c.in_channels * ps * ps;
   char buf[128];
@@ -52,12 +62,13 @@ void Builder::build_mmdit() {
   Ref cew = param("context_embedder.weight", SDN_P_MAT, C, c.joint_dim), ceb = param("context_embedder.bias", SDN_P_VEC_F32, C, 0);
 
   // ---- ALL adaLN linears stacked into one [sum, C] matrix: one GEMM per forward ----
-  // column layout per block i: img 6C at col_img[i], ctx 6C (2C for the last, context_pre_only block) at col_ctx[i]
+  // column layout per block i: img 6C (9C in a dual-attention block) at col_img[i], ctx 6C (2C for the last, context_pre_only block) at col_ctx[i]
   std::vector<int> col_img(L), col_ctx(L);
   int total = 0;
   std::vector<std::pair<std::string, int>> lins, adws, adbs;
   for (int i = 0; i < L; ++i) {
-    col_img[i] = total; lins.push_back({nm(i, "norm1.linear"), 6 * C}); total += 6 * C;
+    const int ni = dual(i) ? 9 * C : 6 * C;
+    col_img[i] = total; lins.push_back({nm(i, "norm1.linear"), ni}); total += ni;
     const int nc = (i == L - 1) ? 2 * C : 6 * C;
     col_ctx[i] = total; lins.push_back({nm(i, "norm1_context.linear"), nc}); total += nc;
   }
@@ -99,7 +110,8 @@ void Builder::build_mmdit() {
   for (int i = 0; i < L; ++i) {
     const bool last = (i == L - 1);
     const int ci = col_img[i], cc = col_ctx[i];
-    // AdaLayerNormZero chunk order: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
+    // AdaLayerNormZero chunk order: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp (SD35AdaLayerNormZeroX of a
+    // dual-attention block: the same six, then shift_msa2, scale_msa2, gate_msa2)
     // AdaLayerNormContinuous (last block's context): scale, shift
     Ref qkvw = stacked({nm(i, "attn.to_q.weight"), nm(i, "attn.to_k.weight"), nm(i, "attn.to_v.weight")}, C, C);
     Ref qkvb; { Ref r0 = param(nm(i, "attn.to_q.bias"), SDN_P_VEC_F32, C, 0); param(nm(i, "attn.to_k.bias"), SDN_P_VEC_F32, C, 0); param(nm(i, "attn.to_v.bias"), SDN_P_VEC_F32, C, 0); qkvb = r0; }
@@ -108,6 +120,19 @@ void Builder::build_mmdit() {
     Ref ow = param(nm(i, "attn.to_out.0.weight"), SDN_P_MAT, C, C), ob = param(nm(i, "attn.to_out.0.bias"), SDN_P_VEC_F32, C, 0);
     Ref f1w = param(nm(i, "ff.net.0.proj.weight"), SDN_P_MAT, 4 * C, C), f1b = param(nm(i, "ff.net.0.proj.bias"), SDN_P_VEC_F32, 4 * C, 0);
     Ref f2w = param(nm(i, "ff.net.2.weight"), SDN_P_MAT, C, 4 * C), f2b = param(nm(i, "ff.net.2.bias"), SDN_P_VEC_F32, C, 0);
+    // SD-3.5: per-head RMS-norm gains of q / k (the last block's norm_added_q is in the checkpoint although its text output is
+    // discarded), and the dual-attention block's image-only attn2; its chunks of norm1.linear: 6 shift_msa2, 7 scale_msa2, 8 gate_msa2
+    Ref nq, nk, naq, nak, q2w, q2b, o2w, o2b, n2q, n2k;
+    if (qkn) {
+      nq = param(nm(i, "attn.norm_q.weight"), SDN_P_VEC_F32, c.head_dim, 0); nk = param(nm(i, "attn.norm_k.weight"), SDN_P_VEC_F32, c.head_dim, 0);
+      naq = param(nm(i, "attn.norm_added_q.weight"), SDN_P_VEC_F32, c.head_dim, 0); nak = param(nm(i, "attn.norm_added_k.weight"), SDN_P_VEC_F32, c.head_dim, 0);
+    }
+    if (dual(i)) {
+      q2w = stacked({nm(i, "attn2.to_q.weight"), nm(i, "attn2.to_k.weight"), nm(i, "attn2.to_v.weight")}, C, C);
+      { Ref r0 = param(nm(i, "attn2.to_q.bias"), SDN_P_VEC_F32, C, 0); param(nm(i, "attn2.to_k.bias"), SDN_P_VEC_F32, C, 0); param(nm(i, "attn2.to_v.bias"), SDN_P_VEC_F32, C, 0); q2b = r0; }
+      o2w = param(nm(i, "attn2.to_out.0.weight"), SDN_P_MAT, C, C); o2b = param(nm(i, "attn2.to_out.0.bias"), SDN_P_VEC_F32, C, 0);
+      if (qkn) { n2q = param(nm(i, "attn2.norm_q.weight"), SDN_P_VEC_F32, c.head_dim, 0); n2k = param(nm(i, "attn2.norm_k.weight"), SDN_P_VEC_F32, c.head_dim, 0); }
+    }
 
     Act xn = act((int64_t)B * N, C, N);
     ln_mod(x, (int64_t)B * N, N, fcol(ci + 1 * C), fcol(ci + 0 * C), total, xn);
@@ -118,6 +143,7 @@ void Builder::build_mmdit() {
     gemm_ex(GemmSpec((int64_t)B * N, 3 * C, C, R(xn), qkvw, qkvb, R(qx)));
     gemm_ex(GemmSpec((int64_t)B * T, 3 * C, C, R(cn), aqkvw, aqkvb, R(qc)));
     drop(xn); drop(cn);
+    if (qkn) { qk_rmsnorm(qx, (int64_t)B * N, nq, nk); qk_rmsnorm(qc, (int64_t)B * T, naq, nak); }
     Act ax = act((int64_t)B * N, C, N), ac = act((int64_t)B * T, C, T);
     {
       Op o; o.kind = OP_ATTN; o.batch = B; o.heads = c.num_heads; o.nq = N + T; o.nk = N + T; o.hd = c.head_dim;
@@ -134,7 +160,36 @@ void Builder::build_mmdit() {
     // image stream: x += gate_msa * to_out(attn);  x += gate_mlp * ff(LNmod(x))
     Act x2 = act((int64_t)B * N, C, N);
     gemm_ex(GemmSpec((int64_t)B * N, C, C, R(ax), ow, ob, R(x2)).with_residual(R(x)).with_rowgate(fcol(ci + 2 * C), N, total));
-    drop(ax); drop(x);
+    drop(ax);
+    if (dual(i)) {
+      // x2 += gate_msa2 * attn2.to_out(attn2(LN(x) (1 + scale_msa2) + shift_msa2)): self-attention over the image tokens alone;
+      // both modulated inputs come from the block's input x, which therefore lives until here
+      Act xn2 = act((int64_t)B * N, C, N);
+      ln_mod(x, (int64_t)B * N, N, fcol(ci + 7 * C), fcol(ci + 6 * C), total, xn2);
+      drop(x);
+      Act q2 = act((int64_t)B * N, 3 * C, N);
+      gemm_ex(GemmSpec((int64_t)B * N, 3 * C, C, R(xn2), q2w, q2b, R(q2)));
+      drop(xn2);
+      if (qkn) qk_rmsnorm(q2, (int64_t)B * N, n2q, n2k);
+      Act a2 = act((int64_t)B * N, C, N);
+      {
+        Op o; o.kind = OP_ATTN; o.batch = B; o.heads = c.num_heads; o.nq = N; o.nk = N; o.hd = c.head_dim;
+        o.a = R(q2); o.k = Ref{SP_WS, q2.off + (int64_t)C * es}; o.v = Ref{SP_WS, q2.off + (int64_t)2 * C * es}; o.out = R(a2);
+        o.ldq = o.ldk = o.ldv = 3 * C; o.ldo = C; o.scale = 1.0f / sqrtf((float)c.head_dim);
+        o.flops = 4.0 * (double)B * o.heads * (double)N * (double)N * o.hd;
+        o.bytes = es * (double)B * N * C * 4.0;
+        if (es == 4) snprintf(o.label, sizeof(o.label), u->mcfg.dtype == 3 ? "k_attention_x3" : "k_attention_f32");
+        else snprintf(o.label, sizeof(o.label), "k_attn<%d>", o.hd);
+        emit(o);
+      }
+      drop(q2);
+      Act x2b = act((int64_t)B * N, C, N);
+      gemm_ex(GemmSpec((int64_t)B * N, C, C, R(a2), o2w, o2b, R(x2b)).with_residual(R(x2)).with_rowgate(fcol(ci + 8 * C), N, total));
+      drop(a2); drop(x2);
+      x2 = x2b;
+    } else {
+      drop(x);
+    }
     Act xm = act((int64_t)B * N, C, N);
     ln_mod(x2, (int64_t)B * N, N, fcol(ci + 4 * C), fcol(ci + 3 * C), total, xm);
     Act hx = act((int64_t)B * N, 4 * C, N);

@@ -78,6 +78,9 @@ static int launch_op_f32(const sdn_unet* u, const Op& o, const Call& P, bool x3,
            : (x3 ? sdn_gemm_x3 : sdn_gemm_f32)(&o.gd, P(o.a), P(o.a2), P(o.w), (const float*)P(o.bias), (const float*)P(o.rowbias),
                                                (const float*)P(o.rowgate), P(o.residual), (void*)P(o.out), stream);
       break;
+    case OP_QK_RMSNORM:                          // dtype 2 and 3 both store f32
+      rc = sdn_qk_rmsnorm(2, (void*)P(o.a), o.rows, o.heads, o.ldq, (const float*)P(o.w), (const float*)P(o.bias), o.eps, stream);
+      break;
     case OP_SPLIT3:
       rc = sdn_split3((const float*)P(o.a), (const float*)P(o.a2), o.rows, o.c1, o.c2, (void*)P(o.out), stream);
       break;
@@ -257,6 +260,9 @@ static int launch_op_16(const sdn_unet* u, const Op& o, const Call& P, bool f16,
       break;
     case OP_RMSNORM:
       rc = sdn_rmsnorm(f16 ? 1 : 0, P(o.a), o.mod, o.rows, o.c1, o.eps, (const float*)P(o.w), (void*)P(o.out), stream);
+      break;
+    case OP_QK_RMSNORM:
+      rc = sdn_qk_rmsnorm(f16 ? 1 : 0, (void*)P(o.a), o.rows, o.heads, o.ldq, (const float*)P(o.w), (const float*)P(o.bias), o.eps, stream);
       break;
     case OP_EMBED:
       rc = sdn_embed_tokens(f16 ? 1 : 0, (const int32_t*)P(o.a), P(o.w), o.rows, o.c1, o.c2, (float*)P(o.out), stream);

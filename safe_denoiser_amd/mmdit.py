@@ -14,6 +14,9 @@ from ._model import ALL_DTYPES, P_POS_CROP, EngineModel  # noqa: F401
 
 SD3_MEDIUM = dict(in_channels=16, out_channels=16, sample_size=64, patch_size=2, num_layers=24, num_attention_heads=24,
                   attention_head_dim=64, joint_attention_dim=4096, pooled_projection_dim=2048, pos_embed_max_size=192)
+# SD-3.5-medium (diffusers >= 0.31): per-head RMS norm of q and k in every attention, a second image-only attention in blocks 0 ... 12
+SD35_MEDIUM = dict(SD3_MEDIUM, pos_embed_max_size=384, qk_norm="rms_norm", dual_attention_layers=tuple(range(13)))
+QK_NORM_GAINS = (".norm_q.weight", ".norm_k.weight", ".norm_added_q.weight", ".norm_added_k.weight")
 
 
 class SD3Transformer2DModel(EngineModel):
@@ -22,13 +25,22 @@ class SD3Transformer2DModel(EngineModel):
     dtype=torch.float32 selects the fp32 precision plan (sdn_mmdit_config.dtype 2): weights, text, pooled projections and
     activations stay f32 and the contractions run on the f32-input matrix cores.  precision = "bf16x3" (with dtype=torch.float32,
     or alone) keeps the f32 storage and forms every contraction as three bf16 products (dtype 3, sdn_gemm_x3); "fp32" = dtype 2.
-    Same meaning as UNet2DConditionModel's arguments."""
+    Same meaning as UNet2DConditionModel's arguments.
+    qk_norm = "rms_norm" and dual_attention_layers = (i, ...) are the SD-3.5 additions (sdn_mmdit_ext, include/sdn.h); with neither
+    the handle is sdn_mmdit_create's."""
 
-    def __init__(self, text_len: int = 333, dtype=torch.float16, precision: str | None = None, **config):
+    def __init__(self, text_len: int = 333, dtype=torch.float16, precision: str | None = None, qk_norm: str | None = None,
+                 dual_attention_layers=(), **config):
         code = self._storage(dtype, precision, ALL_DTYPES,
                              "storage dtype must be torch.bfloat16, torch.float16 or torch.float32 (the precision mode)")
         cfg = dict(SD3_MEDIUM)
         cfg.update(config)
+        if qk_norm not in (None, "rms_norm"):
+            raise NotImplementedError(f'qk_norm = {qk_norm!r} is not implemented by the engine\'s plan (needs None or "rms_norm")')
+        dual = tuple(sorted(set(int(i) for i in (dual_attention_layers or ()))))
+        if dual and not (0 <= dual[0] and dual[-1] < min(cfg["num_layers"], 64)):
+            raise _lib.SdnError(f"dual_attention_layers {dual} must name blocks below num_layers = {cfg['num_layers']} (and below 64)")
+        cfg.update(qk_norm=qk_norm, dual_attention_layers=dual)
         self.config = SimpleNamespace(**cfg)
         self.in_channels = cfg["in_channels"]
         self.text_len = text_len
@@ -37,7 +49,11 @@ class SD3Transformer2DModel(EngineModel):
                              num_heads=cfg["num_attention_heads"], head_dim=cfg["attention_head_dim"],
                              joint_dim=cfg["joint_attention_dim"], pooled_dim=cfg["pooled_projection_dim"],
                              text_len=text_len, time_dim=256, dtype=code)
-        self._create("sdn_mmdit_create", c)
+        if qk_norm or dual:
+            ext = _lib.MmditExt(qk_norm=1 if qk_norm else 0, qk_norm_eps=1e-6, dual_attention_mask=sum(1 << i for i in dual))
+            self._create("sdn_mmdit_create_ex", c, ext)
+        else:
+            self._create("sdn_mmdit_create", c)
 
     # ---- parameters -------------------------------------------------------------------------------------
     def _source_shape(self, p: dict) -> tuple:
@@ -58,6 +74,10 @@ class SD3Transformer2DModel(EngineModel):
         for name, shape in self.state_dict_shapes().items():
             if name == "pos_embed.pos_embed":
                 sd[name] = 0.5 * torch.randn(shape, generator=g)
+            elif name.endswith(QK_NORM_GAINS):
+                # U(1, 3): the 1-D rule below would make gains of about 0 (attention that ignores q and k), and with gains near 1
+                # dropping the norms moves a small network's output less than the bf16 bound -- a test would not see it
+                sd[name] = 1.0 + 2.0 * torch.rand(shape, generator=g)
             elif len(shape) == 1:
                 sd[name] = 0.2 * (torch.rand(shape, generator=g) - 0.5)
             else:

@@ -105,7 +105,7 @@ class SD3SafeDenoiserPipeline:
             scheduler = FlowMatchEulerDiscreteScheduler.from_pretrained(model_dir, subfolder="scheduler")
         dt16 = torch_dtype if torch_dtype in (torch.bfloat16, torch.float16) else torch.float16
         tdir = os.path.join(model_dir, "transformer")
-        tcfg = dict(ck.mmdit_kwargs(ck.read_config(tdir)), sample_size=image_length // 8)
+        tcfg = dict(ck.mmdit_kwargs(ck.read_config(tdir), sd35=True), sample_size=image_length // 8)
         tsd = ck.load_weights(tdir, weights_variant)
         text_len = CLIP_SEQUENCE_LENGTH + MAX_SEQUENCE_LENGTH
         hi = schedule = None
