@@ -113,11 +113,12 @@ def unet_kwargs(cfg: dict) -> dict:
     return out
 
 
-def mmdit_kwargs(cfg: dict, sd35: bool = False) -> dict:
+def mmdit_kwargs(cfg: dict, sd35: bool = False, max_width: int = 2048) -> dict:
     """SD3Transformer2DModel(**kwargs) from transformer/config.json (the SD-v3 family; SD3-medium's file).  Without `sd35` the plan
     has no q/k RMS norm and no second attention per block (the SD-3.5 additions); with it, qk_norm = "rms_norm" and a list of
     dual_attention_layers are accepted and returned (SD-3.5-medium's file).  Either way the text projection is as wide as the
-    blocks, and that width is at most 2048 (SD-3.5-large is 2432 wide)."""
+    blocks, and that width is at most `max_width`: 2048 unless the caller passes the engine's mmdit.MAX_WIDTH = 2560, which admits
+    SD-3.5-large (2432 wide); a width above 2048 must be a multiple of 128 (the wide LayerNorm forms' rule)."""
     dual = cfg.get("dual_attention_layers") or ()
     if not sd35:
         _require(cfg, "transformer", qk_norm=None)
@@ -141,9 +142,12 @@ def mmdit_kwargs(cfg: dict, sd35: bool = False) -> dict:
             "joint_attention_dim", "pooled_projection_dim", "pos_embed_max_size")
     out = {k: cfg[k] for k in keys if k in cfg}
     if sd35:
-        if heads * hd > 2048:
+        if heads * hd > max_width:
             raise NotImplementedError(f"transformer: width num_attention_heads * attention_head_dim = {heads} * {hd} = {heads * hd} is "
-                                      "not implemented by the engine's plan (needs at most 2048; SD-3.5-large is 2432 wide)")
+                                      f"not implemented by the engine's plan (needs at most {max_width}; SD-3.5-large is 2432 wide)")
+        if heads * hd > 2048 and (heads * hd) % 128:
+            raise NotImplementedError(f"transformer: width num_attention_heads * attention_head_dim = {heads} * {hd} = {heads * hd} is "
+                                      "not implemented by the engine's plan (a width above 2048 must be a multiple of 128)")
         out.update(qk_norm=cfg.get("qk_norm"), dual_attention_layers=tuple(dual))
     return out
 

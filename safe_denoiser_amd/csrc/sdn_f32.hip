@@ -1014,7 +1014,7 @@ k_expand3_weights(const float* __restrict__ w, long rows, int cols, int group, u
 // ================================================================================================
 // MMDiT front end and adaLN in f32 (sdn_mmdit_config.dtype 2 / 3).
 // adaLN LayerNorm: out = LN(x) * (1 + scale[b]) + shift[b], scale / shift per-sample f32 rows of leading dimension ld_mod (sample of
-// a row = row / rows_per_batch).  One wave per row, the row in registers (NV float4 per lane: C <= 256 NV); mean, then the centred
+// a row = row / rows_per_batch).  One wave per row, the row in registers (NV float4 per lane: C <= 256 NV, NV <= 10); mean, then the centred
 // sum of squares, both f32 over the registers (the reference's fp32 layer_norm); one 16-byte store per lane and quad.
 template <int NV>
 __global__ void __launch_bounds__(256)
@@ -1413,14 +1413,24 @@ extern "C" int sdn_clip_embed_f32(const int32_t* input_ids, const void* token_em
 }
 
 // ---- MMDiT in the fp32-storage modes (sdn_mmdit_config.dtype 2 / 3) --------------------------------------------------------------
+// The wide adaLN form, 2048 < c <= 2560 with c % 128 == 0 (SD-3.5-large: 2432; arguments checked by the caller): NV = 10, a lane
+// holds 40 f32 elements; the quads past c / 4 of the last two j load zeros and store nothing.
+static int layernorm_mod_f32_wide(const void* x, int64_t rows, int32_t c, float eps, const float* scale, const float* shift,
+                                  int32_t ld_mod, int32_t rows_per_batch, void* out, void* stream) {
+  hipLaunchKernelGGL((k_layernorm_mod_f32<10>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
+                     (long)rows, c, eps, scale, shift, ld_mod, rows_per_batch, (float*)out);
+  record_norm_launch({11, 2, 10, 0, 0, 0, 0, 0, 0, 0, 0, 0});
+  return sdn_launch_status();
+}
 extern "C" int sdn_layernorm_mod_f32(const void* x, int64_t rows, int32_t c, float eps, const float* scale, const float* shift,
                                      int32_t ld_mod, int32_t rows_per_batch, void* out, void* stream) {
-  if (!x || !scale || !shift || !out || rows < 0 || c <= 0 || (c & 3) || c > 2048 || rows_per_batch <= 0 || ld_mod < c ||
+  if (!x || !scale || !shift || !out || rows < 0 || c <= 0 || (c & 3) || (c > 2048 && (c > 2560 || c % 128)) /* = sdn_norm.hip's ln_width_ok above 2048 */ || rows_per_batch <= 0 || ld_mod < c ||
       (ld_mod & 3) || !al16(x) || !al16(scale) || !al16(shift) || !al16(out))
     return SDN_E_INVALID;
   if (rows == 0) return SDN_OK;
   const long blocks = (rows + 3) / 4;
   if (blocks > 0x7fffffffL) return SDN_E_INVALID;
+  if (c > 2048) return layernorm_mod_f32_wide(x, rows, c, eps, scale, shift, ld_mod, rows_per_batch, out, stream);
 #define SDN_LNM_F32(NV)                                                                                                         \
   do { hipLaunchKernelGGL((k_layernorm_mod_f32<NV>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)x, (long)rows, \
                      c, eps, scale, shift, ld_mod, rows_per_batch, (float*)out);                                                \

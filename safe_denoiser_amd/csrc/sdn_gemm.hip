@@ -696,6 +696,12 @@ int dispatch_up4(int nrep, const GemmArgs& g, hipStream_t st) {
   return sdn_launch_status();
 }
 
+// A/B only (g_gemm_variant 7, tools/ab_gemm_wide_n.py): the 128-wide tile on 256 rows (NREP 4, WGM 4: 8 waves, 1 block/CU) for the
+// N > 2048 that neither 256 nor 320 divides (2432, 7296: SD-3.5-large's output projections, FF2 and QKV).  Not selected by any plan:
+// measured against the 128 x 128 tile in profiles/sd35_large_gemm_ab.json.
+template <typename T>
+int launch_tall4(const GemmArgs& g, hipStream_t st) { return launch_dma<T, 4, 4>(g, st); }
+
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace sdn_gemm_detail
@@ -870,7 +876,9 @@ static int sdn_gemm_impl(int dtype, const sdn_gemm_desc* d, const void* a, const
   if (!x3 && d->out_kind == SDN_OUT_BF16 && ((g.ldc & 7) || !al16(out))) return SDN_E_INVALID;
   if (x3 && (g.ldc & 3)) return SDN_E_INVALID;
   const int bn = 32 * nrep;
-  const int bm = nrep >= 8 ? 256 : 128;
+  const bool tall4 = g_gemm_variant == 7 && nrep == 4 && !up4 && !h8 && !x3 && !ln_c && !ln_d && !col_stats && d->split_k <= 1 && !partials &&
+                     d->a_mode == SDN_A_PLAIN && d->N > 2048 && d->N % 256 != 0 && d->N % 320 != 0;      // (A/B: launch_tall4)
+  const int bm = (nrep >= 8 || tall4) ? 256 : 128;
   g.tiles_m = (d->M + bm - 1) / bm; g.tiles_n = d->N / bn;
   {
     const long res_rows = d->residual_bcast ? (long)d->rows_per_batch : (long)d->M;
@@ -938,6 +946,7 @@ static int sdn_gemm_impl(int dtype, const sdn_gemm_desc* d, const void* a, const
     if (rc != SDN_GEMM_NOT_SLAB) { ++g_gemm_launches[0]; return rc; }
   }
   ++g_gemm_launches[1];
+  if (tall4) return dtype == 0 ? launch_tall4<SdnBF16>(g, st) : launch_tall4<SdnF16>(g, st);
   return dtype == 0 ? dispatch_dma<SdnBF16>(nrep, g, st) : dispatch_dma<SdnF16>(nrep, g, st);
 }
 

@@ -440,13 +440,36 @@ int groupnorm_impl(const void* x, const void* x2, int32_t batch, int32_t hw, int
   return sdn_launch_status();
 }
 
+// Row widths of the one-wave-per-row LayerNorm forms: whole 16-byte chunks up to 2048 (NQ <= 4); above that only the 128-multiples
+// up to 2560 (NQ = 5: a lane holds 40 f32 elements; SD-3.5-large is 2432 wide, 48 of the last chunk's 64 lanes live).
+inline bool ln_width_ok(int c) { return c > 0 && !(c & 7) && (c <= 2048 || (c <= 2560 && c % 128 == 0)); }
+
+// The wide forms, 2048 < c <= 2560 (arguments checked by the callers below): k_layernorm<T, 5, 1> and k_row_stats<T, 5, 1>, one row
+// per wave, the lanes past c / 8 - 256 idle in the last chunk (they load and store nothing and add zeros to the butterflies).
+template <typename T>
+int layernorm_wide(const void* x, int64_t rows, int32_t c, float eps, const float* gamma, const float* beta, void* out, void* stream,
+                   int mod, int rows_per_batch, int ld_mod) {
+  hipLaunchKernelGGL((k_layernorm<T, 5, 1>), dim3((unsigned)((rows + 3) / 4)), dim3(THREADS), 0, (hipStream_t)stream,
+                     (const unsigned short*)x, (long)rows, c, eps, gamma, beta, (unsigned short*)out, mod, rows_per_batch, ld_mod);
+  record_norm_launch({mod ? 4 : 3, T::kDtype, 5, 1, 0, 0, 0, 0, 0, 0, 0, 0});
+  return sdn_launch_status();
+}
+template <typename T>
+int row_stats_wide(const void* x, int64_t rows, int32_t c, float eps, float* out, void* stream) {
+  hipLaunchKernelGGL((k_row_stats<T, 5, 1>), dim3((unsigned)((rows + 3) / 4)), dim3(THREADS), 0, (hipStream_t)stream,
+                     (const unsigned short*)x, (long)rows, c, eps, out);
+  record_norm_launch({5, T::kDtype, 5, 1, 0, 0, 0, 0, 0, 0, 0, 0});
+  return sdn_launch_status();
+}
+
 template <typename T>
 int layernorm_impl(const void* x, int64_t rows, int32_t c, float eps, const float* gamma, const float* beta, void* out,
                    void* stream, int mod = 0, int rows_per_batch = 0, int ld_mod = 0) {
-  if (!x || !gamma || !beta || !out || rows < 0 || c <= 0 || (c & 7) || c > 2048) return SDN_E_INVALID;
+  if (!x || !gamma || !beta || !out || rows < 0 || !ln_width_ok(c)) return SDN_E_INVALID;
   if (!al16(x) || !al16(out) || !al16(gamma) || !al16(beta)) return SDN_E_INVALID;
   if (mod && (rows_per_batch <= 0 || ld_mod < c || (ld_mod & 3))) return SDN_E_INVALID;
   if (rows == 0) return SDN_OK;
+  if (c > 2048) return layernorm_wide<T>(x, rows, c, eps, gamma, beta, out, stream, mod, rows_per_batch, ld_mod);
 #define SDN_LN_LAUNCH(NQ, R)                                                                                          \
   do { hipLaunchKernelGGL((k_layernorm<T, NQ, R>), dim3((unsigned)((rows + 4 * (R) - 1) / (4 * (R)))), dim3(THREADS), 0,      \
                      (hipStream_t)stream, (const unsigned short*)x, (long)rows, c, eps, gamma, beta, (unsigned short*)out, \
@@ -537,8 +560,9 @@ int temb_impl(float timestep, int32_t batch, int32_t dim, void* out, void* strea
 
 template <typename T>
 int row_stats_impl(const void* x, int64_t rows, int32_t c, float eps, float* out, void* stream) {
-  if (!x || !out || rows < 0 || c <= 0 || (c & 7) || c > 2048 || !al16(x) || (reinterpret_cast<uintptr_t>(out) & 7)) return SDN_E_INVALID;
+  if (!x || !out || rows < 0 || !ln_width_ok(c) || !al16(x) || (reinterpret_cast<uintptr_t>(out) & 7)) return SDN_E_INVALID;
   if (rows == 0) return SDN_OK;
+  if (c > 2048) return row_stats_wide<T>(x, rows, c, eps, out, stream);
 #define SDN_RS_LAUNCH(NQ, R)                                                                                          \
   do { hipLaunchKernelGGL((k_row_stats<T, NQ, R>), dim3((unsigned)((rows + 4 * (R) - 1) / (4 * (R)))), dim3(THREADS), 0,      \
                      (hipStream_t)stream, (const unsigned short*)x, (long)rows, c, eps, out);                            \

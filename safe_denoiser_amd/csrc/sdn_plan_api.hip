@@ -57,7 +57,7 @@ int sdn_mmdit_create_ex(const sdn_mmdit_config* cfg, const sdn_mmdit_ext* ext, s
       C % 128 != 0 || cfg->joint_dim % 64 != 0 || cfg->pooled_dim % 64 != 0 || cfg->time_dim % 64 != 0 ||
       (cfg->in_channels * cfg->patch_size * cfg->patch_size) % 64 != 0 ||
       (cfg->out_channels * cfg->patch_size * cfg->patch_size) % 32 != 0 || cfg->text_len <= 0 || cfg->dtype < 0 ||
-      cfg->dtype > 3 || C > 2048)
+      cfg->dtype > 3 || C > 2560)
     return SDN_E_INVALID;
   if (ext) {                                                   // the SD-3.5 additions: NULL or all zero = the SD3 plan
     if (ext->qk_norm < 0 || ext->qk_norm > 1 || (ext->qk_norm == 1 && !(ext->qk_norm_eps > 0.f))) return SDN_E_INVALID;

@@ -76,6 +76,17 @@ void Builder::build_mmdit() {
   for (const auto& m : lins) { adws.push_back({m.first + ".weight", m.second}); adbs.push_back({m.first + ".bias", m.second}); }
   Ref adw = stacked(adws, C), adb = stacked(adbs, 0);
   u->tproj_total = total;
+  // The 16-bit GEMM addresses an operand with 31-bit byte offsets (sdn_gemm_impl refuses N K 2 >= 2^31).  Where the whole stacked
+  // matrix passes that (38 blocks of 2432: 5.4 GB; every SD3 / SD-3.5-medium plan stays one group) the GEMM is emitted per group of
+  // whole members, each group into a modulation buffer of its own; a member's columns then live at (buffer, leading dimension) of
+  // its group.  The parameters stay one contiguous stack either way.
+  struct ModGroup { int col0, cols; Act buf; };
+  std::vector<ModGroup> groups(1, ModGroup{0, 0, Act{}});
+  for (const auto& m : lins) {
+    if (es == 2 && groups.back().cols > 0 && ((int64_t)groups.back().cols + m.second) * C * es >= ((int64_t)1 << 31))
+      groups.push_back(ModGroup{groups.back().col0 + groups.back().cols, 0, Act{}});
+    groups.back().cols += m.second;
+  }
 
   // ---- conditioning: silu(time_emb + pooled_emb) -> all modulation vectors ----
   plan->tscalar_off = arena.alloc(256);
@@ -92,10 +103,17 @@ void Builder::build_mmdit() {
   Act scond = act(B, C);                                                         // silu(time_emb + pooled_emb)
   gemm_ex(GemmSpec(B, C, C, R(ph), p2w, p2b, R(scond)).with_act(SDN_ACT_SILU).with_rowbias(R(temb), 1, C));
   drop(ph); drop(temb);
-  Act mods = act(B, total, 0, 0, 4);
-  tproj = R(mods);
-  gemm_ex(GemmSpec(B, total, C, R(scond), adw, adb, R(mods)).with_out_kind(SDN_OUT_F32));
+  for (ModGroup& g : groups) {
+    g.buf = act(B, g.cols, 0, 0, 4);
+    gemm_ex(GemmSpec(B, g.cols, C, R(scond), Ref{SP_W, adw.off + (int64_t)g.col0 * C * es}, Ref{SP_W, adb.off + (int64_t)g.col0 * 4}, R(g.buf))
+                .with_out_kind(SDN_OUT_F32));
+  }
+  tproj = R(groups[0].buf);
   drop(scond);
+  // column `col` of the stacked modulation: the buffer of its group and that group's leading dimension
+  auto group_of = [&](int col) -> const ModGroup& { size_t i = groups.size() - 1; while (groups[i].col0 > col) --i; return groups[i]; };
+  auto fcol = [&](int col) { const ModGroup& g = group_of(col); return Ref{SP_WS, g.buf.off + (int64_t)(col - g.col0) * 4}; };
+  auto fld = [&](int col) { return group_of(col).cols; };
 
   // ---- token streams ----
   Act patches = act((int64_t)B * N, KP);
@@ -135,10 +153,10 @@ void Builder::build_mmdit() {
     }
 
     Act xn = act((int64_t)B * N, C, N);
-    ln_mod(x, (int64_t)B * N, N, fcol(ci + 1 * C), fcol(ci + 0 * C), total, xn);
+    ln_mod(x, (int64_t)B * N, N, fcol(ci + 1 * C), fcol(ci + 0 * C), fld(ci), xn);
     Act cn = act((int64_t)B * T, C, T);
-    if (last) ln_mod(ctx, (int64_t)B * T, T, fcol(cc + 0 * C), fcol(cc + 1 * C), total, cn);
-    else ln_mod(ctx, (int64_t)B * T, T, fcol(cc + 1 * C), fcol(cc + 0 * C), total, cn);
+    if (last) ln_mod(ctx, (int64_t)B * T, T, fcol(cc + 0 * C), fcol(cc + 1 * C), fld(cc), cn);
+    else ln_mod(ctx, (int64_t)B * T, T, fcol(cc + 1 * C), fcol(cc + 0 * C), fld(cc), cn);
     Act qx = act((int64_t)B * N, 3 * C, N), qc = act((int64_t)B * T, 3 * C, T);
     gemm_ex(GemmSpec((int64_t)B * N, 3 * C, C, R(xn), qkvw, qkvb, R(qx)));
     gemm_ex(GemmSpec((int64_t)B * T, 3 * C, C, R(cn), aqkvw, aqkvb, R(qc)));
@@ -159,13 +177,13 @@ void Builder::build_mmdit() {
     drop(qx); drop(qc);
     // image stream: x += gate_msa * to_out(attn);  x += gate_mlp * ff(LNmod(x))
     Act x2 = act((int64_t)B * N, C, N);
-    gemm_ex(GemmSpec((int64_t)B * N, C, C, R(ax), ow, ob, R(x2)).with_residual(R(x)).with_rowgate(fcol(ci + 2 * C), N, total));
+    gemm_ex(GemmSpec((int64_t)B * N, C, C, R(ax), ow, ob, R(x2)).with_residual(R(x)).with_rowgate(fcol(ci + 2 * C), N, fld(ci)));
     drop(ax);
     if (dual(i)) {
       // x2 += gate_msa2 * attn2.to_out(attn2(LN(x) (1 + scale_msa2) + shift_msa2)): self-attention over the image tokens alone;
       // both modulated inputs come from the block's input x, which therefore lives until here
       Act xn2 = act((int64_t)B * N, C, N);
-      ln_mod(x, (int64_t)B * N, N, fcol(ci + 7 * C), fcol(ci + 6 * C), total, xn2);
+      ln_mod(x, (int64_t)B * N, N, fcol(ci + 7 * C), fcol(ci + 6 * C), fld(ci), xn2);
       drop(x);
       Act q2 = act((int64_t)B * N, 3 * C, N);
       gemm_ex(GemmSpec((int64_t)B * N, 3 * C, C, R(xn2), q2w, q2b, R(q2)));
@@ -184,19 +202,19 @@ void Builder::build_mmdit() {
       }
       drop(q2);
       Act x2b = act((int64_t)B * N, C, N);
-      gemm_ex(GemmSpec((int64_t)B * N, C, C, R(a2), o2w, o2b, R(x2b)).with_residual(R(x2)).with_rowgate(fcol(ci + 8 * C), N, total));
+      gemm_ex(GemmSpec((int64_t)B * N, C, C, R(a2), o2w, o2b, R(x2b)).with_residual(R(x2)).with_rowgate(fcol(ci + 8 * C), N, fld(ci)));
       drop(a2); drop(x2);
       x2 = x2b;
     } else {
       drop(x);
     }
     Act xm = act((int64_t)B * N, C, N);
-    ln_mod(x2, (int64_t)B * N, N, fcol(ci + 4 * C), fcol(ci + 3 * C), total, xm);
+    ln_mod(x2, (int64_t)B * N, N, fcol(ci + 4 * C), fcol(ci + 3 * C), fld(ci), xm);
     Act hx = act((int64_t)B * N, 4 * C, N);
     gemm_ex(GemmSpec((int64_t)B * N, 4 * C, C, R(xm), f1w, f1b, R(hx)).with_act(SDN_ACT_GELU_TANH));
     drop(xm);
     Act x3 = act((int64_t)B * N, C, N);
-    gemm_ex(GemmSpec((int64_t)B * N, C, 4 * C, R(hx), f2w, f2b, R(x3)).with_residual(R(x2)).with_rowgate(fcol(ci + 5 * C), N, total));
+    gemm_ex(GemmSpec((int64_t)B * N, C, 4 * C, R(hx), f2w, f2b, R(x3)).with_residual(R(x2)).with_rowgate(fcol(ci + 5 * C), N, fld(ci)));
     drop(hx); drop(x2);
     x = x3;
     // text stream (skipped in the last block: context_pre_only)
@@ -205,15 +223,15 @@ void Builder::build_mmdit() {
       Ref g1w = param(nm(i, "ff_context.net.0.proj.weight"), SDN_P_MAT, 4 * C, C), g1b = param(nm(i, "ff_context.net.0.proj.bias"), SDN_P_VEC_F32, 4 * C, 0);
       Ref g2w = param(nm(i, "ff_context.net.2.weight"), SDN_P_MAT, C, 4 * C), g2b = param(nm(i, "ff_context.net.2.bias"), SDN_P_VEC_F32, C, 0);
       Act c2 = act((int64_t)B * T, C, T);
-      gemm_ex(GemmSpec((int64_t)B * T, C, C, R(ac), aow, aob, R(c2)).with_residual(R(ctx)).with_rowgate(fcol(cc + 2 * C), T, total));
+      gemm_ex(GemmSpec((int64_t)B * T, C, C, R(ac), aow, aob, R(c2)).with_residual(R(ctx)).with_rowgate(fcol(cc + 2 * C), T, fld(cc)));
       drop(ctx);
       Act cm = act((int64_t)B * T, C, T);
-      ln_mod(c2, (int64_t)B * T, T, fcol(cc + 4 * C), fcol(cc + 3 * C), total, cm);
+      ln_mod(c2, (int64_t)B * T, T, fcol(cc + 4 * C), fcol(cc + 3 * C), fld(cc), cm);
       Act hc = act((int64_t)B * T, 4 * C, T);
       gemm_ex(GemmSpec((int64_t)B * T, 4 * C, C, R(cm), g1w, g1b, R(hc)).with_act(SDN_ACT_GELU_TANH));
       drop(cm);
       Act c3 = act((int64_t)B * T, C, T);
-      gemm_ex(GemmSpec((int64_t)B * T, C, 4 * C, R(hc), g2w, g2b, R(c3)).with_residual(R(c2)).with_rowgate(fcol(cc + 5 * C), T, total));
+      gemm_ex(GemmSpec((int64_t)B * T, C, 4 * C, R(hc), g2w, g2b, R(c3)).with_residual(R(c2)).with_rowgate(fcol(cc + 5 * C), T, fld(cc)));
       drop(hc); drop(c2);
       ctx = c3;
     } else {
@@ -224,7 +242,7 @@ void Builder::build_mmdit() {
   // ---- norm_out (AdaLayerNormContinuous: scale, shift) + proj_out + unpatchify ----
   const int col_out = total - 2 * C;
   Act xo = act((int64_t)B * N, C, N);
-  ln_mod(x, (int64_t)B * N, N, fcol(col_out), fcol(col_out + C), total, xo);
+  ln_mod(x, (int64_t)B * N, N, fcol(col_out), fcol(col_out + C), fld(col_out), xo);
   drop(x);
   const int PO = ps * ps * c.out_channels;
   Ref pw = param("proj_out.weight", SDN_P_MAT, PO, C), pb = param("proj_out.bias", SDN_P_VEC_F32, PO, 0);
@@ -234,7 +252,7 @@ void Builder::build_mmdit() {
   { Op o; o.kind = OP_UNPATCHIFY; o.batch = B; o.c1 = c.out_channels; o.hw = S; o.patch = ps; o.a = R(tok); o.out = Ref{SP_OUT, 0};
     o.bytes = (double)B * N * PO * 8.0; snprintf(o.label, sizeof(o.label), "k_unpatchify"); emit(o); }
   drop(tok);
-  drop(mods);
+  for (ModGroup& g : groups) drop(g.buf);
   plan->ws_bytes = arena.peak;
 }
 

@@ -16,6 +16,10 @@ SD3_MEDIUM = dict(in_channels=16, out_channels=16, sample_size=64, patch_size=2,
                   attention_head_dim=64, joint_attention_dim=4096, pooled_projection_dim=2048, pos_embed_max_size=192)
 # SD-3.5-medium (diffusers >= 0.31): per-head RMS norm of q and k in every attention, a second image-only attention in blocks 0 ... 12
 SD35_MEDIUM = dict(SD3_MEDIUM, pos_embed_max_size=384, qk_norm="rms_norm", dual_attention_layers=tuple(range(13)))
+# SD-3.5-large: 38 blocks, 38 heads of 64 (2432 wide), q/k RMS norm, no dual-attention blocks
+SD35_LARGE = dict(SD3_MEDIUM, num_layers=38, num_attention_heads=38, qk_norm="rms_norm")
+# widest block the plan runs (sdn_mmdit_create_ex; above 2048 a multiple of 128: the NQ = 5 LayerNorm forms)
+MAX_WIDTH = 2560
 QK_NORM_GAINS = (".norm_q.weight", ".norm_k.weight", ".norm_added_q.weight", ".norm_added_k.weight")
 
 
@@ -108,7 +112,8 @@ class SD3Transformer2DModel(EngineModel):
 
     def max_samples(self) -> int:
         """Largest batch ONE launch plan addresses (31-bit LDS-DMA offsets per operand): the widest 16-bit operand is the feed-forward
-        hidden state, tokens x 4 x width x 2 B per sample -- 170 samples at 512^2, 42 at 1024^2 for SD3-medium.  `forward_into` runs
+        hidden state, tokens x 4 x width x 2 B per sample -- 170 samples at 512^2, 42 at 1024^2 for SD3-medium (1536 wide); 107 and 26 for
+        SD-3.5-large (2432 wide; 53 and 13 in the fp32-storage plans).  `forward_into` runs
         larger batches as consecutive row blocks (samples do not interact; one handle: this plan keeps no per-text cache).
         fp32-storage plans (precision "fp32" / "bf16x3"): the same rule at 4 B per element -- 85 samples at 512^2, 21 at 1024^2.  Their
         kernels (sdn_gemm_f32 / sdn_gemm_x3, the f32 attention, LayerNorm, patchify and unpatchify) address every operand with 64-bit

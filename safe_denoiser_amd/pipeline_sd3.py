@@ -95,7 +95,7 @@ class SD3SafeDenoiserPipeline:
         import os
 
         from . import checkpoint as ck
-        from .mmdit import SD3Transformer2DModel
+        from .mmdit import MAX_WIDTH, SD3Transformer2DModel
         from .schedulers import FlowMatchEulerDiscreteScheduler
         from .text_sd3 import CLIP_SEQUENCE_LENGTH, MAX_SEQUENCE_LENGTH, SD3TextFrontEnd
         from .vae import AutoencoderKL
@@ -105,7 +105,7 @@ class SD3SafeDenoiserPipeline:
             scheduler = FlowMatchEulerDiscreteScheduler.from_pretrained(model_dir, subfolder="scheduler")
         dt16 = torch_dtype if torch_dtype in (torch.bfloat16, torch.float16) else torch.float16
         tdir = os.path.join(model_dir, "transformer")
-        tcfg = dict(ck.mmdit_kwargs(ck.read_config(tdir), sd35=True), sample_size=image_length // 8)
+        tcfg = dict(ck.mmdit_kwargs(ck.read_config(tdir), sd35=True, max_width=MAX_WIDTH), sample_size=image_length // 8)
         tsd = ck.load_weights(tdir, weights_variant)
         text_len = CLIP_SEQUENCE_LENGTH + MAX_SEQUENCE_LENGTH
         hi = schedule = None

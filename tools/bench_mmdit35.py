@@ -8,7 +8,12 @@ per-kernel rows of one profiled forward (HIP events around every launch: sdn_une
 (k_qk_rmsnorm, k_layernorm) one line per (kernel, rows, width) with the algorithmic bytes of the plan over the measured time.
 To compare with another commit, copy this file into that commit's tools/ directory and run it there with --config sd3-medium (the
 configurations are looked up lazily, so a tree without SD35_MEDIUM still runs SD3-medium); alternate the two commands to see the
-run-to-run spread before reading a difference."""
+run-to-run spread before reading a difference.
+
+SD-3.5-large (38 blocks, 2432 wide) beside SD-3.5-medium, with the full-size row check (the B = 2 forward is finite and each of its
+rows equals that row's B = 1 forward, bit for bit):
+
+    python tools/bench_mmdit35.py --config sd35-medium,sd35-large --batch 8 --iters 10 --check-rows --out profiles/sd35_large.json"""
 import argparse
 import collections
 import ctypes as C
@@ -23,7 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import safe_denoiser_amd as sda  # noqa: E402
 from safe_denoiser_amd import mmdit  # noqa: E402
 
-CONFIGS = {"sd3-medium": lambda: mmdit.SD3_MEDIUM, "sd35-medium": lambda: mmdit.SD35_MEDIUM}
+CONFIGS = {"sd3-medium": lambda: mmdit.SD3_MEDIUM, "sd35-medium": lambda: mmdit.SD35_MEDIUM, "sd35-large": lambda: mmdit.SD35_LARGE}
 NORM_KERNELS = ("k_qk_rmsnorm", "k_layernorm")
 
 
@@ -43,7 +48,7 @@ def per_op_rows(m):
     return agg
 
 
-def measure(name, batch, side, iters, dtype):
+def measure(name, batch, side, iters, dtype, check_rows=False):
     cfg = dict(CONFIGS[name](), sample_size=side)
     m = mmdit.SD3Transformer2DModel(dtype=dtype, **cfg)
     m.load_synthetic_on_device(3)
@@ -59,6 +64,14 @@ def measure(name, batch, side, iters, dtype):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(); call(); e1.record(); torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1))
+    rows_ok = None
+    if check_rows:                                              # full plan at B = 2: finite, and every row is its own B = 1 forward
+        y2 = m(x[:2], timestep=900.0, encoder_hidden_states=e[:2], pooled_projections=pl[:2])[0]
+        y1 = [m(x[i:i + 1], timestep=900.0, encoder_hidden_states=e[i:i + 1], pooled_projections=pl[i:i + 1])[0] for i in range(2)]
+        torch.cuda.synchronize()
+        rows_ok = dict(finite=bool(torch.isfinite(y2).all()), rows_equal_b1=bool(torch.equal(y2[:1], y1[0]) and torch.equal(y2[1:], y1[1])),
+                       std=float(y2.float().std()))
+        print(f"{name}: B = 2 forward {rows_ok}")
     fl, at = m.flops(batch)
     m.profile_next(); call(); torch.cuda.synchronize()
     rows = sorted(m.profile_read(), key=lambda r: -r["ms"])
@@ -73,7 +86,7 @@ def measure(name, batch, side, iters, dtype):
                parameters=sum(torch.Size(s).numel() for k, s in m.state_dict_shapes().items() if k != "pos_embed.pos_embed"),
                kernels=[dict(r, tflops=(r["flops"] / r["ms"] / 1e9) if r["ms"] > 0 else None,
                              tb_per_s=(r["bytes"] / r["ms"] / 1e9) if r["ms"] > 0 else None) for r in rows],
-               norm_kernels=norm_rows)
+               norm_kernels=norm_rows, b2_row_check=rows_ok)
     print(f"{name} side {side} B={batch} {dtype}: {med:.2f} ms per forward (min {min(ts):.2f}, max {max(ts):.2f}), {fl / med / 1e9:.1f} TFLOP/s")
     for r in rows[:14]:
         print(f"  {r['kernel']:20s} x{r['launches']:4d} {r['ms']:8.3f} ms  {(r['flops'] / r['ms'] / 1e9) if r['flops'] else 0:7.1f} TF/s  "
@@ -87,7 +100,8 @@ def measure(name, batch, side, iters, dtype):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--config", choices=list(CONFIGS) + ["both"], default="both")
+    ap.add_argument("--config", default="both", help="one of %s, a comma-separated list of them, or both (= the two medium ones)" % ", ".join(CONFIGS))
+    ap.add_argument("--check-rows", action="store_true", help="also run the plan at B = 2 and compare each row with its B = 1 forward")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--side", type=int, default=64)
     ap.add_argument("--iters", type=int, default=20)
@@ -95,8 +109,9 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "this measurement needs an MI355X"
-    names = list(CONFIGS) if a.config == "both" else [a.config]
-    res = dict(runs=[measure(n, a.batch, a.side, a.iters, getattr(torch, a.dtype)) for n in names])
+    names = ["sd3-medium", "sd35-medium"] if a.config == "both" else a.config.split(",")
+    assert all(n in CONFIGS for n in names), names
+    res = dict(runs=[measure(n, a.batch, a.side, a.iters, getattr(torch, a.dtype), a.check_rows) for n in names])
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
